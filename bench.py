@@ -16,8 +16,14 @@ reference's column interleave render.cpp:90 re-cut as tiles); total work per ste
 The photon maps are built once (per rank, from the same seed: identical, no communication) and
 their build time is reported separately (photon_map_s), as SURVEY.md §8(d) prescribes.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the
+last step's output with `--dump-outputs DIR` and prints one JSON line. `--full` adds what takes
+time of its own or checks the result: cpu_baseline (the oracle/ C++ restatement timed on this
+host's cores) and image_check (the frame's hash against the recorded 1-GPU frame; a mismatch
+fails the run).
+
 Extra JSON fields: roofline (k-NN radiance kernel, algorithmic bytes = 16 B per photon
-returned), cpu_baseline (the oracle/ C++ restatement on this host's cores).
+returned; from the timed steps' own in-library HIP events).
 """
 import argparse
 import hashlib
@@ -51,7 +57,14 @@ def parse():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--scene", default="cornell.scn", help="scene under tests/scenes (C2: cornell)")
     ap.add_argument("--extra", default="", help="extra reference flags, e.g. '-dof 4 12.2 0.025'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline (cpu_baseline) and check the frame's hash "
+                         "against the recorded 1-GPU frame (image_check); off: both are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned to "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-res", type=int, default=32,
                     help="CPU baseline sample: res x res px at the same aa (BASELINE.md section 3)")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -61,7 +74,10 @@ def parse():
     ap.add_argument("--balance", type=int, default=0,
                     help="N: render every tile shard s/N of the frame in turn on this GPU and print "
                          "the per-shard times (min/mean/max: an N-GPU frame takes the slowest)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def shard_balance(a):
@@ -229,6 +245,24 @@ def cpu_baseline(a):
             "calibration": CPU_CALIBRATION if a.scene == "cornell.scn" else None}
 
 
+DUMP_LIMIT = 60 * 1000 * 1000  # bytes of array data over all files of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as path/<name>.npy in float32. Each file gets an equal share of
+    DUMP_LIMIT; an output larger than its share is cut to a fixed sample of its elements (a
+    seeded choice without replacement, in ascending order: the same for every run of the same
+    shape)."""
+    os.makedirs(path, exist_ok=True)
+    room = DUMP_LIMIT // max(1, len(arrays)) // 4  # float32 elements per file
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.size > room:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=room, replace=False))
+            x = x.ravel()[idx]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def device_list(n):
     """Devices of the single-process device set: GI_DEVICES (e.g. "0,0") or 0..n-1."""
     env = os.environ.get("GI_DEVICES")
@@ -303,11 +337,13 @@ def main():
         if world == 1:
             rgb, st = r.RenderImage(aa, w, h)
             last["rgb"] = rgb
+            last["out"] = {"rgb": rgb}
             return st
         import gi_dist
         img, st = gi_dist.render_sharded(r, aa, w, h, a.tile, rank, world, dist, dev)
         if img is not None:
             last["rgb"] = img[0] if isinstance(img, tuple) else None
+            last["out"] = {"rgb": img[0], "rgbf": img[1]} if isinstance(img, tuple) else {"rgbf": img}
         return st
 
     def barrier():
@@ -376,6 +412,14 @@ def main():
     value = samples_per_step * a.steps / elapsed / 1e6
     ms_per_step = elapsed / a.steps * 1000.0
 
+    if a.dump_outputs and rank == 0:
+        # the last timed step's return: the 8-bit frame (a shard run: its packed device buffer,
+        # f32 RGB + the u8 RGB word per owned pixel, the f32 part)
+        if shard is not None:
+            dump_outputs(a.dump_outputs, {"shard_rgbf": shard_buf.cpu().numpy()[:, :3]})
+        else:
+            dump_outputs(a.dump_outputs, last.get("out", {}))
+
     # what ran where: every rank's HIP device and PCI bus, the RCCL
     # communicator's rank count, so a multi-GPU line proves N distinct GPUs took part
     info = r.device_info()
@@ -430,14 +474,14 @@ def main():
         roofline["frame_frac"] = round(frame_ach / (HBM_PEAK_GBPS * n_gpus), 5)
         roofline["frame_bytes_per_sample"] = round(frame_bytes / (samples_per_step * a.steps), 1)
         cpu = None
-        if not a.no_cpu_baseline and n_gpus == 1:
+        if a.full and not a.no_cpu_baseline and n_gpus == 1:
             cpu = cpu_baseline(a)
         rgb = last.get("rgb")
         sha = hashlib.sha256(rgb.tobytes()).hexdigest()[:16] if rgb is not None else None
         want = EXPECTED_SHA16.get((a.scene, a.res, a.aa, a.global_photons, a.caustic_photons,
                                    a.seed, a.extra.strip()))
         check = None
-        if sha is not None and want is not None:
+        if a.full and sha is not None and want is not None:
             check = {"expected_1gpu": want, "equal": sha == want}
         par = {"single": "1 GPU",
                "device-set": f"one process, device set {devices}: tiles{a.tile}x{a.tile} % {n_gpus}, "

@@ -85,6 +85,22 @@ def test_bench_device_set_matches_one_gpu():
     assert topo["comm_count"] in (0, 2)
 
 
+def test_bench_dump_outputs_is_the_timed_frame(tmp_path):
+    """--dump-outputs writes the last timed step's 8-bit frame as float32 (the frame the line's
+    image_sha16 hashes), the same from run to run; a plain run leaves the --full legs out."""
+    import hashlib
+    lines = [run_bench(["--gpus", "1", "--steps", "2", "--dump-outputs", str(tmp_path / d)], {})
+             for d in ("a", "b")]
+    a, b = (np.load(tmp_path / d / "rgb.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (48, 48, 3)
+    np.testing.assert_array_equal(a, b)
+    assert 0.0 <= a.min() < a.max() <= 255.0
+    assert hashlib.sha256(a.astype(np.uint8).tobytes()).hexdigest()[:16] == lines[0]["image_sha16"]
+    for ln in lines:
+        assert ln["steps"] == 2 and len(ln["step_ms"]) == 2 and ln["ms_per_step"] > 0
+        assert ln["cpu_baseline"] is None and ln["image_check"] is None
+
+
 def test_bench_torchrun_packed_matches_one_gpu():
     one = run_bench(["--gpus", "1"], {})
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
