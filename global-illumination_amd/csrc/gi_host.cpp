@@ -360,6 +360,10 @@ struct gi_ctx {
   int mc_persist = -1;            // Monte Carlo paths in mc_persist_kernel with this many blocks
                                   // (GI_MC_PERSIST; 0: mc_kernel, one path per lane; -1: auto)
   DBuf prim_rgb;                  // per-primary sums of the reduction
+  DBuf d_rays, d_ray_ids;         // ray mode: the batch's rays and stream ids (gi_render_rays);
+                                  // gi_camera_rays: one chunk of its output
+  std::vector<gi_ray> ray_stage;  // ... gathered in batch order where the batch's pixels are
+  std::vector<uint64_t> id_stage; // not one row-major run (tile shards)
   DBuf ind_tab, mc_tab;           // row -> tile of the tiled indirect entries; owner of MC path 64k
   DBuf ind_trows, ind_rows;       // indirect paths' tiled slots: rows per tile, their scan
   DBuf ind_masks;                 // their rows' query and base masks
@@ -1307,13 +1311,49 @@ int knn_list(gi_ctx *c, int mi, const float4 *qpos, const QShade *qshade, int64_
   return run_knn(c, k, nq, ms);
 }
 
-// render the given output pixels into the device image buffers
+// Ray source of a render (gi_render_rays): spp rays per output pixel, pixel (x, y)'s at
+// [(y * w + x) * spp, ...) of the caller's frame-wide host buffers; ids may be null.
+struct RaySrc {
+  const gi_ray *rays;
+  const uint64_t *ids;
+  int spp;
+};
+
+// the rays (and ids) of the batch's npix pixels onto the device, in batch order: straight from
+// the caller's buffer where the pixels are one row-major run (a full frame's batches), else
+// gathered pixel by pixel first
+int upload_rays(gi_ctx *c, const RaySrc &R, const int32_t *pix_xy, int64_t npix, int w) {
+  const size_t spp = (size_t)R.spp, n = (size_t)npix * spp;
+  const size_t first = (size_t)pix_xy[1] * w + pix_xy[0];
+  bool run = true;
+  for (int64_t k = 1; k < npix && run; k++)
+    run = (size_t)pix_xy[2 * k + 1] * w + pix_xy[2 * k] == first + (size_t)k;
+  const gi_ray *rays = R.rays + first * spp;
+  const uint64_t *ids = R.ids ? R.ids + first * spp : nullptr;
+  if (!run) {
+    c->ray_stage.resize(n);
+    if (R.ids) c->id_stage.resize(n);
+    for (int64_t k = 0; k < npix; k++) {
+      const size_t src = ((size_t)pix_xy[2 * k + 1] * w + pix_xy[2 * k]) * spp;
+      memcpy(&c->ray_stage[(size_t)k * spp], R.rays + src, spp * sizeof(gi_ray));
+      if (R.ids) memcpy(&c->id_stage[(size_t)k * spp], R.ids + src, spp * 8);
+    }
+    rays = c->ray_stage.data();
+    ids = R.ids ? c->id_stage.data() : nullptr;
+  }
+  HIPCHK(c, upload(c->d_rays, rays, n * sizeof(gi_ray), c->stream));
+  if (ids) HIPCHK(c, upload(c->d_ray_ids, ids, n * 8, c->stream));
+  return GI_OK;
+}
+
+// render the given output pixels into the device image buffers (rsrc: their primary rays come
+// from the caller instead of the camera, aa is then unused)
 int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &pix_xy,
-                  gi_render_stats *rs) {
+                  gi_render_stats *rs, const RaySrc *rsrc = nullptr) {
   const gi_params &P = c->P;
-  int af = 1 << aa;
-  int dof = std::max(1, P.dof_test);
-  int64_t per_pix = (int64_t)af * af * dof;
+  int af = rsrc ? 1 : 1 << aa;
+  int dof = rsrc ? 1 : std::max(1, P.dof_test);
+  int64_t per_pix = rsrc ? (int64_t)rsrc->spp : (int64_t)af * af * dof;
   int64_t npix_total = (int64_t)pix_xy.size() / 2;
   double knn_ms[2] = {0, 0}, launches[2] = {0, 0};
   HIPCHK(c, upload(c->pixels, pix_xy.data(), pix_xy.size() * 4, c->stream));
@@ -1368,6 +1408,21 @@ int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &p
     a.path_off = c->path_off.as<uint32_t>();
     a.mc_off = c->mc_off.as<uint32_t>();
     a.ind_off = c->ind_off.as<uint32_t>();
+    if (rsrc) {
+      // this batch's slice only (a C2-sized frame's 16.8 M rays are 0.94 GB)
+      auto tu0 = std::chrono::steady_clock::now();
+      int rc = upload_rays(c, *rsrc, pix_xy.data() + 2 * p0, npix, w);
+      if (rc) return rc;
+      a.spp = rsrc->spp;
+      set_ray_slice(a, RaySlice{c->d_rays.as<gi_ray_dev>(),
+                                rsrc->ids ? c->d_ray_ids.as<uint64_t>() : nullptr});
+      if (c->batch_log) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        fprintf(stderr, "[gi] batch %lld: ray upload %lld rays, %.2f ms\n", (long long)nbatch,
+                (long long)nprim,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tu0).count());
+      }
+    }
     // counters before the primary kernel, restored if the batch is re-run smaller
     HIPCHK(c, hipMemcpyAsync(c->stats_bak.p, c->d_stats.p, ST_BYTES, hipMemcpyDeviceToDevice,
                              c->stream));
@@ -1817,8 +1872,10 @@ static void release_scratch(gi_ctx *c) {
                   &c->pcounts, &c->poffs, &c->pbuf, &c->pkeys, &c->pcursor, &c->ptmp, &c->pacc,
                   &c->pglob, &c->ind_cont, &c->ind_ncont, &c->mc_cont, &c->mc_ncont,
                   &c->mc_cont2, &c->mc_ncont2, &c->prim_rgb, &c->ind_tab, &c->mc_tab,
-                  &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack};
+                  &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids};
   for (DBuf *b : bufs) b->release();
+  std::vector<gi_ray>().swap(c->ray_stage);
+  std::vector<uint64_t>().swap(c->id_stage);
   for (auto &b : c->recv) b.release();
   for (auto &b : c->peer_pix) b.release();
   for (int m = 0; m < 2; m++) {
@@ -1917,6 +1974,53 @@ int gi_read_scene(gi_ctx *c, const char *path, int real) {
     if (k) d->scene = c->scene;
     return upload_scene(d);
   });
+}
+
+int gi_get_camera(const gi_ctx *c, gi_camera *out) {
+  if (!c || !out) return GI_ERR_ARG;
+  if (!c->have_scene) return GI_ERR_STATE;
+  const double *r = c->scene.cam_raw;
+  for (int i = 0; i < 3; i++) {
+    out->eye[i] = r[i];
+    out->towards[i] = r[3 + i];
+    out->up[i] = r[6 + i];
+  }
+  out->xfov = r[9];
+  return GI_OK;
+}
+
+int gi_set_camera(gi_ctx *c, const gi_camera *cam) {
+  if (!c || !cam) return GI_ERR_ARG;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded (gi_read_scene)");
+  double r[10];
+  for (int i = 0; i < 3; i++) {
+    r[i] = cam->eye[i];
+    r[3 + i] = cam->towards[i];
+    r[6 + i] = cam->up[i];
+  }
+  r[9] = cam->xfov;
+  for (double v : r)
+    if (!std::isfinite(v)) return fail(c, GI_ERR_ARG, "camera: non-finite value");
+  const double *t = r + 3, *u = r + 6;
+  const double x[3] = {u[1] * t[2] - u[2] * t[1], u[2] * t[0] - u[0] * t[2], u[0] * t[1] - u[1] * t[0]};
+  const double tl = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+  const double ul = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  const double xl = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  if (!(tl > 0.0) || !std::isfinite(tl)) return fail(c, GI_ERR_ARG, "camera: zero towards vector");
+  // parallel within rounding: the sine of the angle between them is below 1e-12
+  if (!(xl > 1e-12 * tl * ul) || !std::isfinite(xl))
+    return fail(c, GI_ERR_ARG, "camera: up vector parallel to towards");
+  if (!(r[9] > 0.0 && r[9] < 1.5707963267948966))
+    return fail(c, GI_ERR_ARG, "camera: xfov outside (0, pi/2)");
+  // the view enters only the primary rays (make_view): the scene upload, the photon maps, their
+  // kd trees and dk bounds and the -cache irradiance stay; the batch size is measured again
+  set_camera(c->scene, r);
+  c->q_per_prim = 0.0;
+  for (gi_ctx *d : c->peers) {
+    set_camera(d->scene, r);
+    d->q_per_prim = 0.0;
+  }
+  return GI_OK;
 }
 
 int gi_scene_info(gi_ctx *c, int *nnodes, int *nlights, int *nprims, double *radius) {
@@ -2131,7 +2235,8 @@ int gi_get_kd_tree(gi_ctx *c, int map, float *nodes, int64_t node_floats, int32_
 }
 
 static int render_common(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &pix,
-                         uint8_t *rgb8, float *rgbf, gi_render_stats *st, bool keep_rgbf) {
+                         uint8_t *rgb8, float *rgbf, gi_render_stats *st, bool keep_rgbf,
+                         const RaySrc *rsrc = nullptr) {
   int rc = check_ready(c);
   if (rc) return rc;
   if (aa < 0 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
@@ -2155,7 +2260,7 @@ static int render_common(gi_ctx *c, int aa, int w, int h, const std::vector<int3
   unsigned long long s[ST_COUNT];
   for (int pass = 0;; pass++) {
     memset(&local, 0, sizeof local);
-    rc = render_pixels(c, aa, w, h, pix, &local);
+    rc = render_pixels(c, aa, w, h, pix, &local, rsrc);
     if (rc) return rc;
     HIPCHK(c, read_stats(c, s));
     if (s[ST_GEN_MISS] == 0) break;
@@ -2244,7 +2349,7 @@ static std::vector<int32_t> shard_pixels(int w, int h, int tile, int shard, int 
 // xGMI when the devices are distinct (each peer's stream feeds its own link into device 0), a
 // peer copy otherwise. Device 0 scatters them into the image; nothing else is exchanged.
 static int render_multi(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *rgbf,
-                        gi_render_stats *st) {
+                        gi_render_stats *st, const RaySrc *rsrc = nullptr) {
   const int nd = 1 + (int)c->peers.size();
   const int tile = 16;
   auto t0 = std::chrono::steady_clock::now();
@@ -2255,7 +2360,7 @@ static int render_multi(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *r
     memset(&ls[k], 0, sizeof ls[k]);
   }
   int rc = on_devices(c, [&](int k, gi_ctx *d) -> int {
-    int r = render_common(d, aa, w, h, pix[k], nullptr, nullptr, &ls[k], false);
+    int r = render_common(d, aa, w, h, pix[k], nullptr, nullptr, &ls[k], false, rsrc);
     if (r || k == 0) return r;
     const int64_t n = (int64_t)pix[k].size() / 2;
     HIPCHK(d, d->pack.ensure((size_t)n * 16));
@@ -2333,24 +2438,83 @@ static int render_multi(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *r
   return GI_OK;
 }
 
-// RenderImage, render.cpp:155-259
-int gi_render_image(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *rgbf,
-                    gi_render_stats *st) {
-  if (!c) return GI_ERR_ARG;
+// full frame on the context's device or device set, from the camera or from a ray source
+static int render_frame(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *rgbf,
+                        gi_render_stats *st, const RaySrc *rsrc) {
   hipSetDevice(c->device);
-  if (!c->peers.empty()) {
-    int rc = check_ready(c);
-    if (rc) return rc;
-    if (aa < 0 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
-    return render_multi(c, aa, w, h, rgb8, rgbf, st);
-  }
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (aa < 0 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  if (!c->peers.empty()) return render_multi(c, aa, w, h, rgb8, rgbf, st, rsrc);
   std::vector<int32_t> pix((size_t)w * h * 2);
   for (int y = 0; y < h; y++)
     for (int x = 0; x < w; x++) {
       pix[2 * ((size_t)y * w + x)] = x;
       pix[2 * ((size_t)y * w + x) + 1] = y;
     }
-  return render_common(c, aa, w, h, pix, rgb8, rgbf, st, false);
+  return render_common(c, aa, w, h, pix, rgb8, rgbf, st, false, rsrc);
+}
+
+// RenderImage, render.cpp:155-259
+int gi_render_image(gi_ctx *c, int aa, int w, int h, uint8_t *rgb8, float *rgbf,
+                    gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  return render_frame(c, aa, w, h, rgb8, rgbf, st, nullptr);
+}
+
+int gi_render_rays(gi_ctx *c, int w, int h, int spp, const gi_ray *rays, const uint64_t *ids,
+                   uint8_t *rgb8, float *rgbf, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  if (!rays) return fail(c, GI_ERR_ARG, "null ray buffer");
+  if (spp < 1) return fail(c, GI_ERR_ARG, "spp must be at least 1");
+  if (w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  if ((int64_t)w * h >= ((int64_t)1 << 31) / spp + (((int64_t)1 << 31) % spp != 0))
+    return fail(c, GI_ERR_ARG, "width * height * spp must be below 2^31");
+  const RaySrc src{rays, ids, spp};
+  return render_frame(c, 0, w, h, rgb8, rgbf, st, &src);
+}
+
+int gi_camera_rays(gi_ctx *c, int aa, int w, int h, gi_ray *rays, uint64_t *ids, int64_t cap,
+                   int64_t *n) {
+  if (!c || !n) return GI_ERR_ARG;
+  hipSetDevice(c->device);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (aa < 0 || aa > 15 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  const gi_params &P = c->P;
+  const int af = 1 << aa, dof = std::max(1, P.dof_test);
+  const int64_t total = (int64_t)w * h * af * af * dof;
+  *n = total;
+  if (!rays) return GI_OK;
+  if (cap < total) return fail(c, GI_ERR_ARG, "ray buffer holds fewer rays than the frame");
+  CameraRaysArgs a;
+  memset(&a, 0, sizeof a);
+  a.cam = make_view(c).cam;
+  a.seed = P.seed;
+  a.dof = P.depth_of_field;
+  a.dof_test = dof;
+  a.af = af;
+  a.W = w * af;
+  a.H = h * af;
+  a.out_w = w;
+  const int64_t chunk = (int64_t)1 << 22;  // 224 MB of rays and ids at a time
+  HIPCHK(c, c->d_rays.ensure((size_t)std::min(chunk, total) * sizeof(gi_ray)));
+  HIPCHK(c, c->d_ray_ids.ensure((size_t)std::min(chunk, total) * 8));
+  a.rays = c->d_rays.as<gi_ray_dev>();
+  a.ids = c->d_ray_ids.as<uint64_t>();
+  for (int64_t s0 = 0; s0 < total; s0 += chunk) {
+    a.first = s0;
+    a.n = std::min(chunk, total - s0);
+    launch_camera_rays(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(rays + s0, c->d_rays.p, (size_t)a.n * sizeof(gi_ray),
+                             hipMemcpyDeviceToHost, c->stream));
+    if (ids)
+      HIPCHK(c, hipMemcpyAsync(ids + s0, c->d_ray_ids.p, (size_t)a.n * 8, hipMemcpyDeviceToHost,
+                               c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GI_OK;
 }
 
 int gi_render_tiles(gi_ctx *c, int aa, int w, int h, int tile, int shard, int nshards,

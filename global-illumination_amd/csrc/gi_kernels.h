@@ -15,6 +15,12 @@ struct gi_photon_dev {
 };
 static_assert(sizeof(gi_photon_dev) == 20, "photon record is 20 bytes");
 
+// caller-supplied primary ray; byte-identical to gi_ray (gi.h)
+struct gi_ray_dev {
+  double org[3], dir[3];
+};
+static_assert(sizeof(gi_ray_dev) == 48, "ray record is 48 bytes");
+
 // per primary sample: the RayTrace state the sample paths need (raytracer.cpp:174-233)
 struct Spawn {
   double p[3], n[3], v[3];
@@ -83,7 +89,7 @@ struct RenderArgs {
   int32_t W, H;         // supersampled viewport (render.cpp:177-178)
   int32_t dof_test;
   int32_t out_w;
-  int64_t nprim;        // npix * af^2 * dof_test
+  int64_t nprim;        // npix * af^2 * dof_test (ray mode: npix * spp)
   int64_t total_paths;
   Spawn *spawn;
   uint32_t *npaths;     // [nprim] 1 + transmissive + specular paths (CSR base slots; the
@@ -110,6 +116,8 @@ struct RenderArgs {
   uint32_t mc_cap_s;
   uint32_t *mc_next;    // mc_persist_kernel's path counter (null: mc_kernel, one path per lane)
   int32_t mc_persist_blocks;  // its grid
+  int32_t spp;          // ray mode (gi_render_rays): rays per output pixel, af = dof_test = 1; 0 in
+                        // camera mode (in what was padding: see ray_slice)
   IndCont *mc_cont2;    // ... those whose first bounce hit glass / a mirror (mc_sub_kernel),
   uint32_t *mc_ncont2;  // at that hit, same stripes and capacity
   // Indirect paths' slots, tiled: primaries b in tiles of 64 (T = b / 64); tile T holds
@@ -146,6 +154,26 @@ struct RenderArgs {
   uint8_t *rgb8;
   unsigned long long *stats;
 };
+
+// Ray mode's batch slice: the caller's rays and stream ids, one per primary sample b (ids null:
+// the ray's index in the caller's frame-wide buffer). It rides in the camera block of the scene
+// view (S.cam), which ray mode does not read, and spp in former padding, so that RenderArgs keeps
+// its size: a larger kernel-argument block moves the argument offsets and scratch copies of every
+// render kernel, and the camera-mode kernels are to stay the code they were.
+struct RaySlice {
+  const gi_ray_dev *rays;
+  const uint64_t *ids;
+};
+static_assert(sizeof(RaySlice) <= sizeof(DCamera), "the ray slice rides in the camera block");
+__host__ __device__ __forceinline__ RaySlice ray_slice(const RenderArgs &a) {
+  RaySlice r;
+  __builtin_memcpy(&r, &a.S.cam, sizeof r);
+  return r;
+}
+inline void set_ray_slice(RenderArgs &a, const RaySlice &r) {
+  __builtin_memset(&a.S.cam, 0, sizeof a.S.cam);
+  __builtin_memcpy(&a.S.cam, &r, sizeof r);
+}
 
 // kd node record (KdView::nodes): lo = {min xyz, split}, hi = {max xyz, axis bits}
 struct KdNode {
@@ -339,6 +367,17 @@ struct PhotonArgs {
 };
 enum { PM_COUNT = 0, PM_EMIT = 1, PM_APPEND = 2 };
 
+// camera_rays_kernel (gi_camera_rays): samples [first, first + n) of the frame
+struct CameraRaysArgs {
+  DCamera cam;
+  uint64_t seed;
+  int32_t dof, dof_test;
+  int32_t af, W, H, out_w;  // as RenderArgs
+  int64_t first, n;
+  gi_ray_dev *rays;         // [n]
+  uint64_t *ids;            // [n]
+};
+
 struct ScanTemp {
   uint32_t *level[8];
   uint32_t *level_out[8];
@@ -347,7 +386,8 @@ struct ScanTemp {
 
 hipError_t launch_scan(const uint32_t *in, uint32_t *out, int64_t n, ScanTemp &tmp,
                        hipStream_t st);
-void launch_primary(const RenderArgs &a, hipStream_t st);
+void launch_primary(const RenderArgs &a, hipStream_t st);  // camera or ray mode (a.spp)
+void launch_camera_rays(const CameraRaysArgs &a, hipStream_t st);
 // wait_join = false: the join event is recorded on st2 but st does not wait for it (the caller
 // makes st wait later, after work that reads only the deterministic query slots)
 void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2 = nullptr,

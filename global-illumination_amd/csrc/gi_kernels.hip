@@ -60,8 +60,9 @@ __global__ void scan_add_kernel(uint32_t *out, const uint32_t *block_off, int64_
 // ---------------------------------------------------------------------------------------
 // Render: primary samples
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void decode_primary(const RenderArgs &a, int64_t b, int &pix, int &i,
-                                               int &j, int &k, uint64_t &psample) {
+// camera mode: sample b of the batch -> pixel, supersampled viewport cell (i, j), lens sample k
+__device__ __forceinline__ void decode_camera(const RenderArgs &a, int64_t b, int &pix, int &i,
+                                              int &j, int &k, uint64_t &psample) {
   // b < nprim <= 2^31 per batch: 32-bit division (64-bit integer division is a long routine)
   uint32_t af2 = (uint32_t)(a.af * a.af), dof = (uint32_t)a.dof_test, ub = (uint32_t)b;
   k = (int)(ub % dof);
@@ -74,8 +75,119 @@ __device__ __forceinline__ void decode_primary(const RenderArgs &a, int64_t b, i
   psample = ((uint64_t)j * (uint64_t)a.W + (uint64_t)i) * (uint64_t)a.dof_test + (uint64_t)k;
 }
 
-// Threadable_RayTracer body (render.cpp:96-132) + RayTrace (raytracer.cpp:174-233) up to the
-// sample fan-outs. Writes the spawn record the path kernels expand.
+// Ray mode (RAYS; RenderArgs::spp > 0): sample b is ray b % spp of output pixel b / spp; its stream id
+// is the caller's, or the ray's index in the caller's frame-wide buffer (pixels row-major)
+// RAYS is a template parameter of the path kernels, not a branch on a.spp: the camera-mode
+// instances are then the instruction streams they were before ray mode existed (a uniform
+// branch here changed their register allocation and spills).
+template <bool RAYS>
+__device__ __forceinline__ void decode_primary(const RenderArgs &a, int64_t b, int &pix, int &i,
+                                               int &j, int &k, uint64_t &psample) {
+  if (!RAYS) {
+    decode_camera(a, b, pix, i, j, k, psample);
+    return;
+  }
+  uint32_t ub = (uint32_t)b, spp = (uint32_t)a.spp;
+  pix = (int)(ub / spp);
+  k = (int)(ub % spp);
+  int2 pc = a.pixels[pix];
+  i = pc.x;
+  j = pc.y;
+  const uint64_t *ids = ray_slice(a).ids;
+  psample = ids ? ids[b]
+                : ((uint64_t)pc.y * (uint64_t)a.out_w + (uint64_t)pc.x) * (uint64_t)spp + (uint64_t)k;
+}
+
+// The camera's ray through cell (i, j) of the W x H supersampled viewport, render.cpp:96-117:
+// pinhole through the far-plane point, from a lens sample (two or more draws of rng) with depth
+// of field. Shared by primary_kernel and camera_rays_kernel, so that exported rays are the
+// render's own bits.
+__device__ __forceinline__ void camera_ray(const DCamera &cam, int dof, int i, int j, int W, int H,
+                                           Rng &rng, V &eye, V &org, V &dir) {
+  double dx = (double)(2 * (i - W / 2)) / (double)W;
+  double dy = (double)(2 * (j - H / 2)) / (double)H;
+  V far_point = ld3(cam.far_org) + (ld3(cam.far_right) * dx) + (ld3(cam.far_up) * dy);
+  eye = ld3(cam.eye);
+  org = eye;
+  if (dof) {
+    double r1, r2;
+    do {
+      r1 = (rng.next() * 2.0) - 1.0;
+      r2 = (rng.next() * 2.0) - 1.0;
+    } while (r1 * r1 + r2 * r2 > 1.0);
+    org = eye + r1 * ld3(cam.dof_u) + r2 * ld3(cam.dof_v);
+  }
+  dir = normalize(far_point - org);
+}
+
+// RayTrace (raytracer.cpp:174-233) of one primary ray up to the sample fan-outs: intersection,
+// ambient + direct light, fan counts; writes sample b's spawn record, which the path kernels
+// expand. `eye` is the view point the hit is shaded from.
+__device__ __forceinline__ void primary_shade(const RenderArgs &a, int64_t b, V org, V dir, V eye,
+                                              Rng &rng, uint64_t &c_ray, uint64_t &c_shadow,
+                                              uint64_t &c_ind) {
+  const SceneView &S = a.S;
+  const Flags &F = a.F;
+  Spawn sp;
+  sp.hit = 0;
+  sp.tri = -1;
+  sp.n_t = sp.n_s = sp.n_i = 0;
+  sp.q_glob = sp.q_caus = 0;
+  Hit h;
+  Counts cnt = {0, 0, 0, 0, 0, 0};
+  if (!scene_intersect(S, org, dir, h)) {
+    C3 bg = ldc(S.background);
+    sp.base[0] = bg.r; sp.base[1] = bg.g; sp.base[2] = bg.b;
+  } else {
+    c_ray = 1;
+    const DMaterial &m = S.mats[h.mat];
+    C3 color = rgb(0, 0, 0);
+    if (F.ambient) color += ldc(S.ambient);
+    V view = normalize(h.p - eye);
+    double ct = dot(h.n, -view);
+    double R = 0;
+    if (F.ambient && (m.flags & MF_AMBIENT)) color += ldc(m.ka);
+    if (F.direct && (m.flags & (MF_DIFFUSE | MF_SPECULAR)))
+      direct_illumination(S, F, h.p, h.n, eye, color, m, ct, false, rng, cnt);
+    if (F.transmissive && (m.flags & MF_TRANSPARENT)) {
+      if (F.specular && F.fresnel) R = reflection_coeff(F.ir_air, ct, m.ir);
+      if (R < 1.0) {
+        C3 tw = (1.0 - R) * ldc(m.kt);
+        sp.n_t = (int)ceil((F.trans_test * maxch(tw) + F.trans_test) / 2.0);
+      }
+    }
+    if (F.specular && ((m.flags & MF_SPECULAR) || R > 0)) {
+      C3 tw = ldc(m.kt) * R + ldc(m.ks);
+      sp.n_s = (int)ceil((F.spec_test * maxch(tw) + F.spec_test) / 2.0);
+    }
+    if (F.indirect && (m.flags & MF_DIFFUSE)) {
+      sp.n_i = (int)ceil((F.indirect_test * m.max_kd + F.indirect_test) / 2.0);
+      const C3 wt = ldc(m.kd) / (double)sp.n_i;
+      sp.wt[0] = wt.r; sp.wt[1] = wt.g; sp.wt[2] = wt.b;
+    }
+    if (F.caustic && (m.flags & MF_DIFFUSE)) sp.q_caus = 1;
+    if (F.photon_viz && (m.flags & MF_DIFFUSE)) {
+      sp.q_glob = 1;
+      if (!F.cache) c_ind = 1;
+    }
+    sp.hit = 1;
+    sp.p[0] = h.p.x; sp.p[1] = h.p.y; sp.p[2] = h.p.z;
+    sp.n[0] = h.n.x; sp.n[1] = h.n.y; sp.n[2] = h.n.z;
+    sp.v[0] = view.x; sp.v[1] = view.y; sp.v[2] = view.z;
+    sp.ct = ct;
+    sp.R = R;
+    sp.mat = h.mat;
+    sp.tri = h.tri;
+    sp.base[0] = color.r; sp.base[1] = color.g; sp.base[2] = color.b;
+  }
+  a.spawn[b] = sp;
+  a.npaths[b] = 1u + (uint32_t)(sp.n_t + sp.n_s);
+  a.nmc[b] = (uint32_t)(sp.n_t + sp.n_s);
+  a.nind[b] = (uint32_t)sp.n_i;
+  c_shadow = cnt.shadow;
+}
+
+// Threadable_RayTracer body (render.cpp:96-132) + primary_shade.
 // Occupancy target: left free, the soft-light call chain (direct_illumination -> soft_light ->
 // illum_test) took 256 VGPRs + 110 AGPRs, one wave per SIMD; at 2 (32 VGPRs spilled) the C3
 // frame (jensen.scn, 128 + 128 shadow rays per primary hit) is 10 % faster (3 waves: 5 %), the
@@ -87,84 +199,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRIMARY_WPE
   int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t c_ray = 0, c_shadow = 0, c_ind = 0;
   if (b < a.nprim) {
-    const SceneView &S = a.S;
-    const Flags &F = a.F;
     int pix, i, j, k;
     uint64_t psample;
-    decode_primary(a, b, pix, i, j, k, psample);
+    decode_camera(a, b, pix, i, j, k, psample);
     Rng rng;
-    rng.init(F.seed, KIND_PRIMARY, psample, 0);
-    double dx = (double)(2 * (i - a.W / 2)) / (double)a.W;
-    double dy = (double)(2 * (j - a.H / 2)) / (double)a.H;
-    V far_point = ld3(S.cam.far_org) + (ld3(S.cam.far_right) * dx) + (ld3(S.cam.far_up) * dy);
-    V eye = ld3(S.cam.eye);
-    V org = eye;
-    if (F.dof) {
-      double r1, r2;
-      do {
-        r1 = (rng.next() * 2.0) - 1.0;
-        r2 = (rng.next() * 2.0) - 1.0;
-      } while (r1 * r1 + r2 * r2 > 1.0);
-      org = eye + r1 * ld3(S.cam.dof_u) + r2 * ld3(S.cam.dof_v);
-    }
-    V dir = normalize(far_point - org);
-    Spawn sp;
-    sp.hit = 0;
-    sp.tri = -1;
-    sp.n_t = sp.n_s = sp.n_i = 0;
-    sp.q_glob = sp.q_caus = 0;
-    Hit h;
-    Counts cnt = {0, 0, 0, 0, 0, 0};
-    if (!scene_intersect(S, org, dir, h)) {
-      C3 bg = ldc(S.background);
-      sp.base[0] = bg.r; sp.base[1] = bg.g; sp.base[2] = bg.b;
-    } else {
-      c_ray = 1;
-      const DMaterial &m = S.mats[h.mat];
-      C3 color = rgb(0, 0, 0);
-      if (F.ambient) color += ldc(S.ambient);
-      V view = normalize(h.p - eye);
-      double ct = dot(h.n, -view);
-      double R = 0;
-      if (F.ambient && (m.flags & MF_AMBIENT)) color += ldc(m.ka);
-      if (F.direct && (m.flags & (MF_DIFFUSE | MF_SPECULAR)))
-        direct_illumination(S, F, h.p, h.n, eye, color, m, ct, false, rng, cnt);
-      if (F.transmissive && (m.flags & MF_TRANSPARENT)) {
-        if (F.specular && F.fresnel) R = reflection_coeff(F.ir_air, ct, m.ir);
-        if (R < 1.0) {
-          C3 tw = (1.0 - R) * ldc(m.kt);
-          sp.n_t = (int)ceil((F.trans_test * maxch(tw) + F.trans_test) / 2.0);
-        }
-      }
-      if (F.specular && ((m.flags & MF_SPECULAR) || R > 0)) {
-        C3 tw = ldc(m.kt) * R + ldc(m.ks);
-        sp.n_s = (int)ceil((F.spec_test * maxch(tw) + F.spec_test) / 2.0);
-      }
-      if (F.indirect && (m.flags & MF_DIFFUSE)) {
-        sp.n_i = (int)ceil((F.indirect_test * m.max_kd + F.indirect_test) / 2.0);
-        const C3 wt = ldc(m.kd) / (double)sp.n_i;
-        sp.wt[0] = wt.r; sp.wt[1] = wt.g; sp.wt[2] = wt.b;
-      }
-      if (F.caustic && (m.flags & MF_DIFFUSE)) sp.q_caus = 1;
-      if (F.photon_viz && (m.flags & MF_DIFFUSE)) {
-        sp.q_glob = 1;
-        if (!F.cache) c_ind = 1;
-      }
-      sp.hit = 1;
-      sp.p[0] = h.p.x; sp.p[1] = h.p.y; sp.p[2] = h.p.z;
-      sp.n[0] = h.n.x; sp.n[1] = h.n.y; sp.n[2] = h.n.z;
-      sp.v[0] = view.x; sp.v[1] = view.y; sp.v[2] = view.z;
-      sp.ct = ct;
-      sp.R = R;
-      sp.mat = h.mat;
-      sp.tri = h.tri;
-      sp.base[0] = color.r; sp.base[1] = color.g; sp.base[2] = color.b;
-    }
-    a.spawn[b] = sp;
-    a.npaths[b] = 1u + (uint32_t)(sp.n_t + sp.n_s);
-    a.nmc[b] = (uint32_t)(sp.n_t + sp.n_s);
-    a.nind[b] = (uint32_t)sp.n_i;
-    c_shadow = cnt.shadow;
+    rng.init(a.F.seed, KIND_PRIMARY, psample, 0);
+    V eye, org, dir;
+    camera_ray(a.S.cam, a.F.dof, i, j, a.W, a.H, rng, eye, org, dir);
+    primary_shade(a, b, org, dir, eye, rng, c_ray, c_shadow, c_ind);
   }
   wave_add(&a.stats[ST_RAY], c_ray);
   wave_add(&a.stats[ST_SHADOW], c_shadow);
@@ -662,7 +704,7 @@ __global__ __launch_bounds__(256) void slot0_kernel(RenderArgs a) {
 // make all 64 lanes execute the Fresnel pow, refraction trig and Phong-lobe sampling (and hold
 // them idle through the glass bounces). Such paths are queued at the hit (wave-aggregated
 // append) and finish compacted in ind_cont_kernel; the arithmetic and RNG stream are unchanged.
-template <int W, bool SPLIT, uint32_t KINDS>
+template <int W, bool SPLIT, uint32_t KINDS, bool RAYS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void ind_kernel(RenderArgs a) {
   // thread t = tiled entry t (RenderArgs::ind_rows): row t / 64 of tile T, lane = primary
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -680,7 +722,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
     int64_t g = a.ind_g0 + tau;
     int pix, i, j, k;
     uint64_t psample;
-    decode_primary(a, pb, pix, i, j, k, psample);
+    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
     PathCtx P;
     path_init(P, a, g, pb, pslot);
     P.fixed[0] = a.qind_base + tau;  // at most one (global) query per indirect path
@@ -935,7 +977,7 @@ void mc_sub_kernel(RenderArgs a, const IndCont *queue, const uint32_t *fill, uin
 #define MC_WPE 2  // mc_kernel occupancy target (waves per SIMD; 3 measured slower: spills)
 #endif
 // TransmissiveIllumination / SpecularIllumination sample (raytracer.cpp:47-109)
-template <uint32_t KINDS, bool DEFER, bool HARD>
+template <uint32_t KINDS, bool DEFER, bool HARD, bool RAYS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE))) void mc_kernel(RenderArgs a) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   Counts cnt = {0, 0, 0, 0, 0, 0};
@@ -946,7 +988,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
     int64_t g = (int64_t)a.path_off[pb] + 1 + s;
     int pix, i, j, k;
     uint64_t psample;
-    decode_primary(a, pb, pix, i, j, k, psample);
+    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
     const SceneView &S = a.S;
     const Flags &F = a.F;
     const DMaterial &m = S.mats[sp.mat];
@@ -986,7 +1028,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
 // as long as its longest path with the finished lanes idle. Paths are handed out in order by one
 // atomic per wave per refill (mc_next); a path's arithmetic, RNG stream, query keys and base
 // slot do not depend on the lane that runs it, so the image and counters equal mc_kernel's.
-template <uint32_t KINDS, bool DEFER, bool HARD>
+template <uint32_t KINDS, bool DEFER, bool HARD, bool RAYS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE)))
 void mc_persist_kernel(RenderArgs a) {
   const int lane = (int)(threadIdx.x & 63);
@@ -1018,7 +1060,7 @@ void mc_persist_kernel(RenderArgs a) {
         int64_t g = (int64_t)a.path_off[pb] + 1 + s;
         int pix, i, j, k;
         uint64_t psample;
-        decode_primary(a, pb, pix, i, j, k, psample);
+        decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
         const DMaterial &m = S.mats[sp.mat];
         V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
         double ct = sp.ct, R = sp.R;
@@ -1594,7 +1636,8 @@ __global__ __launch_bounds__(256) void reduce_prim_kernel(RenderArgs a) {
 __global__ __launch_bounds__(64) void reduce_kernel(RenderArgs a) {
   int pix = blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= a.npix) return;
-  int af2 = a.af * a.af;
+  // ray mode: the pixel's spp rays take the place of the af^2 sub-cells (one sample each)
+  const int af2 = a.spp ? a.spp : a.af * a.af;
   double acc0 = 0, acc1 = 0, acc2 = 0;
   // row-major subsample order inside the pixel block (render.cpp:207-214 sums j-outer)
   for (int sub = 0; sub < af2; sub++) {
@@ -1611,7 +1654,7 @@ __global__ __launch_bounds__(64) void reduce_kernel(RenderArgs a) {
     s2 = s2 < 0 ? 0 : (s2 > 1.0 ? 1.0 : s2);
     acc0 += s0; acc1 += s1; acc2 += s2;
   }
-  double bw = 1.0 / a.af / a.af;
+  double bw = a.spp ? 1.0 / a.spp : 1.0 / a.af / a.af;
   double r = bw * acc0, g = bw * acc1, b = bw * acc2;
   int2 pc = a.pixels[pix];
   int64_t o = ((int64_t)pc.y * a.out_w + pc.x) * 3;
@@ -1861,6 +1904,54 @@ __global__ void intersect_kernel(SceneView S, int64_t n, const double *org, cons
 // ---------------------------------------------------------------------------------------
 // host-callable launchers
 // ---------------------------------------------------------------------------------------
+// Ray mode's primary stage (gi_render_rays): sample b's ray comes from the batch's uploaded
+// slice (ray_slice, 48 B per ray: three 16-B loads per lane) and is shaded from its own
+// origin. A kernel of its own, so that primary_kernel's register allocation stays as tuned.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRIMARY_WPE))) void primary_rays_kernel(RenderArgs a) {
+  int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t c_ray = 0, c_shadow = 0, c_ind = 0;
+  if (b < a.nprim) {
+    int pix, i, j, k;
+    uint64_t psample;
+    decode_primary<true>(a, b, pix, i, j, k, psample);
+    Rng rng;
+    rng.init(a.F.seed, KIND_PRIMARY, psample, 0);
+    const double2 *r = reinterpret_cast<const double2 *>(ray_slice(a).rays + b);
+    const double2 r0 = r[0], r1 = r[1], r2 = r[2];
+    V org = {r0.x, r0.y, r1.x}, dir = {r1.y, r2.x, r2.y};
+    primary_shade(a, b, org, dir, org, rng, c_ray, c_shadow, c_ind);
+  }
+  wave_add(&a.stats[ST_RAY], c_ray);
+  wave_add(&a.stats[ST_SHADOW], c_shadow);
+  wave_add(&a.stats[ST_INDIRECT], c_ind);
+}
+
+// gi_camera_rays: one thread per camera sample of the frame, samples [first, first + n) in the
+// order pixel (row-major), sub-cell, lens sample; writes the ray camera_ray gives and the
+// sample's stream id (decode_camera's psample)
+__global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs a) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.n) return;
+  const uint64_t s = (uint64_t)(a.first + t);
+  const uint32_t af2 = (uint32_t)(a.af * a.af), dof = (uint32_t)a.dof_test;
+  const int k = (int)(s % dof);
+  const uint64_t r = s / dof;
+  const int sub = (int)(r % af2);
+  const int64_t pix = (int64_t)(r / af2);
+  const int i = (int)(pix % a.out_w) * a.af + (sub % a.af);
+  const int j = (int)(pix / a.out_w) * a.af + (sub / a.af);
+  const uint64_t psample = ((uint64_t)j * (uint64_t)a.W + (uint64_t)i) * (uint64_t)a.dof_test + (uint64_t)k;
+  Rng rng;
+  rng.init(a.seed, KIND_PRIMARY, psample, 0);
+  V eye, org, dir;
+  camera_ray(a.cam, a.dof, i, j, a.W, a.H, rng, eye, org, dir);
+  double2 *o = reinterpret_cast<double2 *>(a.rays + t);
+  o[0] = make_double2(org.x, org.y);
+  o[1] = make_double2(org.z, dir.x);
+  o[2] = make_double2(dir.y, dir.z);
+  a.ids[t] = psample;
+}
+
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 hipError_t launch_scan(const uint32_t *in, uint32_t *out, int64_t n, ScanTemp &tmp,
@@ -1887,16 +1978,20 @@ hipError_t launch_scan(const uint32_t *in, uint32_t *out, int64_t n, ScanTemp &t
 }
 
 void launch_primary(const RenderArgs &a, hipStream_t st) {
-  primary_kernel<<<nblk(a.nprim, 256), 256, 0, st>>>(a);
+  if (a.spp) primary_rays_kernel<<<nblk(a.nprim, 256), 256, 0, st>>>(a);
+  else primary_kernel<<<nblk(a.nprim, 256), 256, 0, st>>>(a);
+}
+void launch_camera_rays(const CameraRaysArgs &a, hipStream_t st) {
+  if (a.n > 0) camera_rays_kernel<<<nblk(a.n, 256), 256, 0, st>>>(a);
 }
 // occupancy: 4 waves per SIMD where the kernel fits 128 VGPRs without spills (triangles and
 // spheres only; C2 ind_kernel 37.8 -> 31.3 ms, frame -2.6 %), else 3 (the 4-wave instances of
 // the other element sets spill 74-129 VGPRs; 3 or 5 waves for triangles and spheres measured
 // slower, profiles/r05_ind_waves_ab.txt)
-template <uint32_t KINDS>
+template <uint32_t KINDS, bool RAYS>
 void launch_ind(const RenderArgs &a, unsigned g, hipStream_t st) {
-  if (KINDS == KINDS_TRI_SPHERE) ind_kernel<4, true, KINDS><<<g, 128, 0, st>>>(a);
-  else ind_kernel<3, true, KINDS><<<g, 128, 0, st>>>(a);
+  if (KINDS == KINDS_TRI_SPHERE) ind_kernel<4, true, KINDS, RAYS><<<g, 128, 0, st>>>(a);
+  else ind_kernel<3, true, KINDS, RAYS><<<g, 128, 0, st>>>(a);
 }
 void launch_cont(const RenderArgs &a, const IndCont *q, const uint32_t *fill, uint32_t cap_s,
                  hipStream_t st) {
@@ -1920,8 +2015,9 @@ static void launch_mc_sub(const RenderArgs &a, hipStream_t st) {
 // on st, so their waves share the CUs instead of running as a low-occupancy tail; st waits for
 // them before returning (fork/join events). The two kernels write disjoint path slots and
 // append queries through the same atomic counters.
-void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_t fork,
-                 hipEvent_t join, bool wait_join) {
+template <bool RAYS>
+static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_t fork,
+                          hipEvent_t join, bool wait_join) {
   const bool side = st2 && fork && join && a.total_mc > 0;
   hipStream_t ms = side ? st2 : st;
   // the Monte Carlo queues' counters are zeroed on st before the fork: a fill on the side stream
@@ -1952,23 +2048,23 @@ void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_
       // persistent: enough blocks to fill the chip at MC_WPE waves per SIMD, or one per 128 paths
       unsigned gp = std::min(g, (unsigned)(a.mc_persist_blocks > 0 ? a.mc_persist_blocks : 1024));
       if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
-        if (a.S.hard_lights) mc_persist_kernel<KINDS_TRI_SPHERE, true, true><<<gp, 128, 0, ms>>>(a);
-        else mc_persist_kernel<KINDS_TRI_SPHERE, true, false><<<gp, 128, 0, ms>>>(a);
+        if (a.S.hard_lights) mc_persist_kernel<KINDS_TRI_SPHERE, true, true, RAYS><<<gp, 128, 0, ms>>>(a);
+        else mc_persist_kernel<KINDS_TRI_SPHERE, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
       } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
-        if (a.S.hard_lights) mc_persist_kernel<KINDS_POLY, true, true><<<gp, 128, 0, ms>>>(a);
-        else mc_persist_kernel<KINDS_POLY, true, false><<<gp, 128, 0, ms>>>(a);
+        if (a.S.hard_lights) mc_persist_kernel<KINDS_POLY, true, true, RAYS><<<gp, 128, 0, ms>>>(a);
+        else mc_persist_kernel<KINDS_POLY, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
       } else {
-        mc_persist_kernel<KINDS_ALL, true, false><<<gp, 128, 0, ms>>>(a);
+        mc_persist_kernel<KINDS_ALL, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
       }
     } else if (a.mc_cont) {
       if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
-        if (a.S.hard_lights) mc_kernel<KINDS_TRI_SPHERE, true, true><<<g, 128, 0, ms>>>(a);
-        else mc_kernel<KINDS_TRI_SPHERE, true, false><<<g, 128, 0, ms>>>(a);
+        if (a.S.hard_lights) mc_kernel<KINDS_TRI_SPHERE, true, true, RAYS><<<g, 128, 0, ms>>>(a);
+        else mc_kernel<KINDS_TRI_SPHERE, true, false, RAYS><<<g, 128, 0, ms>>>(a);
       } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
-        if (a.S.hard_lights) mc_kernel<KINDS_POLY, true, true><<<g, 128, 0, ms>>>(a);
-        else mc_kernel<KINDS_POLY, true, false><<<g, 128, 0, ms>>>(a);
+        if (a.S.hard_lights) mc_kernel<KINDS_POLY, true, true, RAYS><<<g, 128, 0, ms>>>(a);
+        else mc_kernel<KINDS_POLY, true, false, RAYS><<<g, 128, 0, ms>>>(a);
       } else {
-        mc_kernel<KINDS_ALL, true, false><<<g, 128, 0, ms>>>(a);
+        mc_kernel<KINDS_ALL, true, false, RAYS><<<g, 128, 0, ms>>>(a);
       }
     }
     if (a.mc_cont) {
@@ -1979,15 +2075,15 @@ void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_
         launch_cont(a, a.mc_cont, a.mc_ncont, a.mc_cap_s, ms);
       }
     } else {
-      mc_kernel<KINDS_ALL, false, false><<<g, 128, 0, ms>>>(a);
+      mc_kernel<KINDS_ALL, false, false, RAYS><<<g, 128, 0, ms>>>(a);
     }
   }
   if (a.total_ind > 0) {
     unsigned g = nblk(a.tind, 128);
-    if (!a.split_ind) ind_kernel<2, false, KINDS_ALL><<<g, 128, 0, st>>>(a);
-    else if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) launch_ind<KINDS_TRI_SPHERE>(a, g, st);
-    else if ((a.S.kinds & ~KINDS_POLY) == 0) launch_ind<KINDS_POLY>(a, g, st);
-    else launch_ind<KINDS_ALL>(a, g, st);
+    if (!a.split_ind) ind_kernel<2, false, KINDS_ALL, RAYS><<<g, 128, 0, st>>>(a);
+    else if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) launch_ind<KINDS_TRI_SPHERE, RAYS>(a, g, st);
+    else if ((a.S.kinds & ~KINDS_POLY) == 0) launch_ind<KINDS_POLY, RAYS>(a, g, st);
+    else launch_ind<KINDS_ALL, RAYS>(a, g, st);
     // continuations: 32 blocks per stripe stride over its fill
     if (a.split_ind) launch_cont(a, a.ind_cont, a.ind_ncont, a.ind_cap_s, st);
   }
@@ -1995,6 +2091,11 @@ void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_
     (void)hipEventRecord(join, st2);
     if (wait_join) (void)hipStreamWaitEvent(st, join, 0);
   }
+}
+void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_t fork,
+                 hipEvent_t join, bool wait_join) {
+  if (a.spp) launch_path_t<true>(a, st, st2, fork, join, wait_join);
+  else launch_path_t<false>(a, st, st2, fork, join, wait_join);
 }
 // Shard gather of a device set (gi_host.cpp render_multi): a device's output pixels packed in
 // its pixel-list order as {r, g, b, rgb8 bytes} (16 B), and their scatter on the first device.

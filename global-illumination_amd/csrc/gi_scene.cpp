@@ -638,6 +638,24 @@ static Bx flatten(Graph &G, int gi_idx, int parent, HostScene &S) {
 
 }  // namespace
 
+// R3Camera(e, t, u, xfov, xfov) with R3Triad(towards, up) (R3Triad.cpp:72-79)
+void set_camera(HostScene &S, const double cam[10]) {
+  for (int i = 0; i < 10; i++) S.cam_raw[i] = cam[i];
+  P3 eye = p3(cam[0], cam[1], cam[2]);
+  P3 towards = p3(cam[3], cam[4], cam[5]);
+  P3 up = p3(cam[6], cam[7], cam[8]);
+  P3 z = unit(scl(towards, -1.0));
+  P3 x = unit(crs(up, z));
+  P3 y = crs(z, x);
+  for (int i = 0; i < 3; i++) {
+    S.eye[i] = eye.v[i];
+    S.towards[i] = -z.v[i];
+    S.right[i] = x.v[i];
+    S.up[i] = y.v[i];
+  }
+  S.xfov = S.yfov = cam[9];
+}
+
 bool load_scene(const std::string &path, bool real, HostScene &S, std::string &err) {
   S = HostScene();
   Graph G;
@@ -689,32 +707,19 @@ bool load_scene(const std::string &path, bool real, HostScene &S, std::string &e
     S.background[i] = G.background[i];
   }
   S.radius = 0.5 * nrm(p3(sb.mx[0] - sb.mn[0], sb.mx[1] - sb.mn[1], sb.mx[2] - sb.mn[2]));
-  // camera: R3Camera(e, t, u, xfov, xfov) with R3Triad(towards, up); default R3Scene.cpp:557-566
-  P3 eye, towards, up;
-  double xfov;
+  // camera: the file's `camera` command, else the default of R3Scene.cpp:557-566
+  double cam[10];
   if (G.has_camera) {
-    eye = p3(G.cam[0], G.cam[1], G.cam[2]);
-    towards = p3(G.cam[3], G.cam[4], G.cam[5]);
-    up = p3(G.cam[6], G.cam[7], G.cam[8]);
-    xfov = G.cam[9];
+    for (int i = 0; i < 10; i++) cam[i] = G.cam[i];
   } else {
-    towards = p3(0, 0, -1);
-    up = p3(0, 1, 0);
+    P3 towards = p3(0, 0, -1), up = p3(0, 1, 0);
     P3 c = p3(S.centroid[0], S.centroid[1], S.centroid[2]);
     P3 off = scl(towards, 3 * S.radius);
-    eye = sub(c, off);
-    xfov = 0.25;
+    P3 eye = sub(c, off);
+    for (int i = 0; i < 3; i++) { cam[i] = eye.v[i]; cam[3 + i] = towards.v[i]; cam[6 + i] = up.v[i]; }
+    cam[9] = 0.25;
   }
-  P3 z = unit(scl(towards, -1.0));
-  P3 x = unit(crs(up, z));
-  P3 y = crs(z, x);
-  for (int i = 0; i < 3; i++) {
-    S.eye[i] = eye.v[i];
-    S.towards[i] = -z.v[i];
-    S.right[i] = x.v[i];
-    S.up[i] = y.v[i];
-  }
-  S.xfov = S.yfov = xfov;
+  set_camera(S, cam);
   // default lights, R3Scene.cpp:569-583
   if (S.lights.empty()) {
     for (int k = 0; k < 2; k++) {

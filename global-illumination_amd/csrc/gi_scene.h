@@ -17,6 +17,7 @@ struct HostScene {
   // camera (R3Camera: eye + triad, R3Triad.cpp:72-79); xfov = yfov (Q5)
   double eye[3], towards[3], right[3], up[3];
   double xfov = 0.25, yfov = 0.25;
+  double cam_raw[10];  // eye, towards, up, xfov as given (the `camera` command's numbers)
   double ambient[3] = {0, 0, 0}, background[3] = {0, 0, 0};
   double bmin[3], bmax[3];
   double radius = 0, centroid[3] = {0, 0, 0};
@@ -26,5 +27,7 @@ struct HostScene {
 
 // ReadScene (utils/io_utils.cpp:219-250) -> R3Scene::ReadFile (R3Scene.cpp:514-587)
 bool load_scene(const std::string &path, bool real_material, HostScene &out, std::string &err);
+// camera from the `camera` command's ten numbers (raw kept in cam_raw, triad derived)
+void set_camera(HostScene &S, const double cam[10]);
 
 }  // namespace gi

@@ -5,6 +5,8 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
   ReadScene        utils/io_utils.cpp:219-250
   MapPhotons       photonmap.cpp:260-436
   RenderImage      render.cpp:155-259
+  get_camera / set_camera / camera_rays / render_rays: further views from the resident photon
+                   maps (no reference counterpart; gi.h "views from resident photon maps")
   EstimateRadiance utils/photon_utils.cpp:72-162      (batched test seam)
   FindClosestQuick R3Shapes/R3Kdtree.cpp:688-848      (batched test seam)
   Intersects       R3Graphics/R3Scene.cpp:471-479     (batched test seam)
@@ -29,6 +31,7 @@ EXPORTED = [
     "gi_destroy", "gi_last_error",
     "gi_set_params", "gi_read_scene", "gi_scene_info", "gi_map_photons", "gi_set_photon_map",
     "gi_get_photon_map", "gi_get_kd_tree", "gi_set_progress", "gi_render_image", "gi_render_tiles",
+    "gi_get_camera", "gi_set_camera", "gi_camera_rays", "gi_render_rays",
     "gi_render_tiles_packed", "gi_compose_tiles", "gi_quantize",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
@@ -59,6 +62,15 @@ QUERY_DTYPE = np.dtype([
     ("kd", "<f8", 3), ("ks", "<f8", 3), ("shininess", "<f8"), ("max_dist", "<f8"),
     ("k", "<i4"), ("filter", "<i4")])
 
+
+class Camera(C.Structure):
+    """gi_camera: the .scn `camera` command's first ten numbers, as given."""
+    _fields_ = [("eye", C.c_double * 3), ("towards", C.c_double * 3), ("up", C.c_double * 3),
+                ("xfov", C.c_double)]
+
+
+RAY_DTYPE = np.dtype([("org", "<f8", 3), ("dir", "<f8", 3)])  # gi_ray
+assert RAY_DTYPE.itemsize == 48
 
 GI_MAX_DEVICES = 64
 
@@ -140,6 +152,12 @@ def lib():
                                      C.c_int64, P(C.c_int32), P(C.c_int64)]
         L.gi_render_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, P(RenderStats)]
+        L.gi_get_camera.argtypes = [C.c_void_p, P(Camera)]
+        L.gi_set_camera.argtypes = [C.c_void_p, P(Camera)]
+        L.gi_camera_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_int64, P(C.c_int64)]
+        L.gi_render_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, P(RenderStats)]
         L.gi_render_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p, P(RenderStats)]
         L.gi_render_tiles_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -290,6 +308,52 @@ class Renderer:
         self._check(lib().gi_render_image(self._ctx, aa, width, height, rgb.ctypes.data,
                                           rgbf.ctypes.data if want_float else None,
                                           C.byref(st)))
+        stats = _stats_dict(st)
+        return (rgb, rgbf, stats) if want_float else (rgb, stats)
+
+    def get_camera(self):
+        """(eye, towards, up, xfov) the context renders from, as given by the scene file or the
+        last set_camera (tuples of floats; gi_get_camera)."""
+        cam = Camera()
+        self._check(lib().gi_get_camera(self._ctx, C.byref(cam)))
+        return tuple(cam.eye), tuple(cam.towards), tuple(cam.up), cam.xfov
+
+    def set_camera(self, eye, towards, up, xfov):
+        """Render from another camera; scene, photon maps and kd trees stay (gi_set_camera)."""
+        cam = Camera()
+        for i in range(3):
+            cam.eye[i], cam.towards[i], cam.up[i] = float(eye[i]), float(towards[i]), float(up[i])
+        cam.xfov = float(xfov)
+        self._check(lib().gi_set_camera(self._ctx, C.byref(cam)))
+
+    def camera_rays(self, aa, width, height):
+        """The primary rays RenderImage(aa, width, height) traces and their RNG stream ids
+        (gi_camera_rays): (rays [n] RAY_DTYPE, ids [n] uint64), pixels row-major from the bottom
+        row, a pixel's 4^aa * dof_test samples together."""
+        n = C.c_int64(0)
+        self._check(lib().gi_camera_rays(self._ctx, aa, width, height, None, None, 0, C.byref(n)))
+        rays = np.zeros(n.value, dtype=RAY_DTYPE)
+        ids = np.zeros(n.value, dtype=np.uint64)
+        self._check(lib().gi_camera_rays(self._ctx, aa, width, height, rays.ctypes.data,
+                                         ids.ctypes.data, n.value, C.byref(n)))
+        return rays, ids
+
+    def render_rays(self, width, height, spp, rays, ids=None, want_float=False):
+        """Render caller-made primary rays, spp per output pixel (gi_render_rays); returns like
+        RenderImage. ids: RNG stream id per ray (default: the ray's index)."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        need = width * height * spp
+        if spp >= 1 and (len(rays) != need or (ids is not None and len(ids) != need)):
+            raise ValueError(f"{need} rays expected (width * height * spp), got {len(rays)}")
+        rgb = np.zeros((height, width, 3), dtype=np.uint8)
+        rgbf = np.zeros((height, width, 3), dtype=np.float32) if want_float else None
+        st = RenderStats()
+        self._check(lib().gi_render_rays(self._ctx, width, height, spp, rays.ctypes.data,
+                                         None if ids is None else ids.ctypes.data,
+                                         rgb.ctypes.data,
+                                         rgbf.ctypes.data if want_float else None, C.byref(st)))
         stats = _stats_dict(st)
         return (rgb, rgbf, stats) if want_float else (rgb, stats)
 

@@ -4,6 +4,8 @@
 // ParseArgs -> ReadScene -> MapPhotons (if indirect|caustic|photon_viz) -> RenderImage ->
 // WriteImage, with the -v statistics of io_utils.cpp:240-246, photonmap.cpp:416-435 and
 // render.cpp:224-255. Exit codes: 1 for a bad flag, -1 (255) for load/render/write failures.
+// Extension: -camera ex ey ez tx ty tz ux uy uz xfov renders from that camera instead of the
+// scene file's (gi_set_camera; the numbers of the .scn `camera` command).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -35,7 +37,34 @@ static void OnProgress(int stage, double progress, void *user) {
   PrintProgress(progress, PROGRESS_BAR_WIDTH);
 }
 
+// Takes `-camera` and its ten numbers out of argv (gi_parse_args keeps the reference's flag
+// set); false on fewer than ten numbers or a non-number. The last -camera wins.
+static bool TakeCamera(int &argc, char **argv, gi_camera &cam, bool &have) {
+  for (int a = 1; a < argc;) {
+    if (strcmp(argv[a], "-camera")) { a++; continue; }
+    double v[10];
+    for (int k = 0; k < 10; k++) {
+      if (a + 1 + k >= argc) return false;
+      char *end = nullptr;
+      v[k] = strtod(argv[a + 1 + k], &end);
+      if (end == argv[a + 1 + k] || *end) return false;
+    }
+    for (int i = 0; i < 3; i++) { cam.eye[i] = v[i]; cam.towards[i] = v[3 + i]; cam.up[i] = v[6 + i]; }
+    cam.xfov = v[9];
+    have = true;
+    for (int k = a + 11; k < argc; k++) argv[k - 11] = argv[k];
+    argc -= 11;
+  }
+  return true;
+}
+
 int main(int argc, char **argv) {
+  gi_camera cam;
+  bool have_cam = false;
+  if (!TakeCamera(argc, argv, cam, have_cam)) {
+    fprintf(stderr, "Invalid program argument: -camera");
+    return 1;
+  }
   gi_params P;
   gi_params_default(&P);
   const char *scene = nullptr, *out = nullptr, *err = nullptr;
@@ -78,6 +107,11 @@ int main(int argc, char **argv) {
   gi_set_progress(ctx, OnProgress, &prog);
   auto t0 = std::chrono::steady_clock::now();
   if (gi_read_scene(ctx, scene, real) != GI_OK) {
+    fprintf(stderr, "%s\n", gi_last_error(ctx));
+    gi_destroy(ctx);
+    return -1;
+  }
+  if (have_cam && gi_set_camera(ctx, &cam) != GI_OK) {
     fprintf(stderr, "%s\n", gi_last_error(ctx));
     gi_destroy(ctx);
     return -1;

@@ -242,6 +242,48 @@ int gi_render_tiles_packed(gi_ctx *ctx, int aa, int width, int height, int tile_
  * Both packed entry points restore the calling thread's current HIP device on return. */
 int gi_compose_tiles(gi_ctx *ctx, int width, int height, int tile_px, int nshards,
                      const void *packed, int64_t stride, uint8_t *rgb8, float *rgbf);
+/* ---- views from resident photon maps ---------------------------------------------------- */
+/* The photon maps, their kd trees and K-th-distance bounds and the -cache irradiance do not
+ * depend on the view: after one gi_map_photons a context renders any number of cameras
+ * (gi_set_camera + gi_render_image) or caller-made ray batches (gi_render_rays). No reference
+ * counterpart: the reference renders the scene file's camera only. */
+/* The .scn `camera` command's first ten numbers (R3Scene.cpp camera command;
+ * R3Camera(eye, towards, up, xfov, xfov), Q5: yfov = xfov). Raw values as given:
+ * towards/up need not be unit or orthogonal, the triad is built as at scene load. */
+typedef struct gi_camera { double eye[3], towards[3], up[3], xfov; } gi_camera;
+/* The ten numbers the context renders from: the scene file's `camera` line, the default camera
+ * of a file without one (R3Scene.cpp:557-566), or the last gi_set_camera, exactly as given
+ * (set(get()) changes nothing). GI_ERR_STATE before a scene is read. */
+int gi_get_camera(const gi_ctx *ctx, gi_camera *out);
+/* Replace the camera (all devices of a device set); everything else the context holds stays.
+ * GI_ERR_ARG (camera unchanged) for a non-finite value, a zero towards, an up parallel to
+ * towards, or xfov outside (0, pi/2). gi_read_scene resets the camera to the file's. */
+int gi_set_camera(gi_ctx *ctx, const gi_camera *cam);
+
+typedef struct gi_ray { double org[3], dir[3]; } gi_ray;   /* dir: unit, used as given */
+/* The primary rays gi_render_image(aa, width, height) traces, computed on the device by the
+ * render's own camera code: output pixels row-major (row 0 = bottom), within a pixel the 4^aa
+ * sub-cells row-major and within a sub-cell the dof_test lens samples; ids (optional) receives
+ * each ray's RNG stream id. *n = width * height * 4^aa * dof_test; rays == NULL only reports
+ * it, capacity < *n is GI_ERR_ARG. With depth of field the rays are the lens-sampled ones. */
+int gi_camera_rays(gi_ctx *ctx, int aa, int width, int height,
+                   gi_ray *rays, uint64_t *ids, int64_t capacity, int64_t *n);
+/* Render caller-made primary rays (any sensor: panorama, fisheye, orthographic, light-field
+ * slice): pixel p (row-major, row 0 = bottom) is the box-filtered mean of rays [p * spp,
+ * (p + 1) * spp), each clamped to [0, 1] first, as gi_render_image treats a pixel's sub-cells;
+ * same 8-bit truncation. Ray r draws from RNG stream ids[r], or r when ids is NULL. A hit is
+ * shaded as seen from its ray's origin (view = normalize(hit - org)); directions are used as
+ * given, not renormalised. depth_of_field / dof_test are ignored; every other flag, both
+ * photon maps, the counters and device sets behave as in gi_render_image. GI_ERR_ARG for
+ * spp < 1, rays == NULL or width * height * spp >= 2^31.
+ * Replay: gi_render_rays on gi_camera_rays' output with spp = 4^aa returns gi_render_image's
+ * image and counters bit for bit when depth of field is off. With it on, the camera path shades
+ * from the eye (not the lens sample) and has advanced the sample's stream past the lens draws,
+ * so the replay differs; that is accepted. */
+int gi_render_rays(gi_ctx *ctx, int width, int height, int spp,
+                   const gi_ray *rays, const uint64_t *ids /* may be NULL */,
+                   uint8_t *rgb8, float *rgbf, gi_render_stats *stats);
+
 /* Quantise a full float image like RenderImage's SetPixelRGB (truncate 255*c). */
 int gi_quantize(int width, int height, const float *rgbf, uint8_t *rgb8);
 
