@@ -1363,22 +1363,64 @@ struct Image {
   std::vector<float> rgbf;    // box-filtered clamped colour
 };
 
+// The camera of one render_image(aa, width, height): the far plane and the lens axes,
+// render.cpp:64-77
+struct CamFrame {
+  int af = 1, W = 0, H = 0, xc = 0, yc = 0;
+  V3 eye, far_org, far_right, far_up, u, v;
+};
+static CamFrame cam_frame(const Ctx &c, int aa, int width, int height) {
+  const gi_params &P = c.P;
+  const Camera &cam = c.scene.camera;
+  CamFrame f;
+  f.af = (int)pow(2.0, aa);
+  f.W = width * f.af;
+  f.H = height * f.af;
+  f.xc = f.W / 2;
+  f.yc = f.H / 2;
+  f.eye = cam.eye;
+  f.far_org = cam.eye + cam.towards * P.focus_depth;
+  f.far_right = cam.right * tan(cam.xfov) * P.focus_depth;
+  f.far_up = cam.up * tan(cam.yfov) * P.focus_depth;
+  f.u = normalize(cam.up) * P.aperture_radius;
+  f.v = normalize(cam.right) * P.aperture_radius;
+  return f;
+}
+
+// The primary ray of sub-cell (i, j), lens sample k, render.cpp:96-117: returns its stream id,
+// leaves `rng` as that stream past the lens draws. The one ray function of render_image and
+// oracle_camera_rays.
+static uint64_t camera_ray(const Ctx &c, const CamFrame &f, int i, int j, int k, Rng &rng,
+                           V3 &org, V3 &dir) {
+  const gi_params &P = c.P;
+  double dx = (double)(2 * (i - f.xc)) / (double)f.W;
+  double dy = (double)(2 * (j - f.yc)) / (double)f.H;
+  V3 far_point = f.far_org + (f.far_right * dx) + (f.far_up * dy);
+  uint64_t psample = ((uint64_t)j * f.W + i) * (uint64_t)P.dof_test + k;
+  rng = Rng(P.seed, KIND_PRIMARY, psample, 0);
+  org = f.eye;
+  if (P.depth_of_field) {
+    double r1, r2;
+    do {
+      r1 = (rng.next() * 2.0) - 1.0;
+      r2 = (rng.next() * 2.0) - 1.0;
+    } while (r1 * r1 + r2 * r2 > 1.0);
+    org = f.eye + r1 * f.u + r2 * f.v;
+  }
+  dir = normalize(far_point - org);
+  return psample;
+}
+
 static void render_image(const Ctx &c, int aa, int width, int height, Image &img,
                          Counters &total, double *render_s) {
   auto t0 = std::chrono::steady_clock::now();
   const gi_params &P = c.P;
-  int af = (int)pow(2.0, aa);
+  const CamFrame f = cam_frame(c, aa, width, height);
+  int af = f.af;
   double axis_scale = 1.0 / af;
   double box_weight = 1.0 / af / af;
-  int W = width * af, H = height * af;
+  int W = f.W, H = f.H;
   std::vector<Rgb> buf((size_t)W * H);
-  const Camera &cam = c.scene.camera;
-  V3 far_org = cam.eye + cam.towards * P.focus_depth;
-  V3 far_right = cam.right * tan(cam.xfov) * P.focus_depth;
-  V3 far_up = cam.up * tan(cam.yfov) * P.focus_depth;
-  V3 u = normalize(cam.up) * P.aperture_radius;
-  V3 v = normalize(cam.right) * P.aperture_radius;
-  int xc = W / 2, yc = H / 2;
   int T = std::max(1, P.threads);
   std::vector<Counters> cnts(T);
   auto work = [&](int id) {
@@ -1390,26 +1432,14 @@ static void render_image(const Ctx &c, int aa, int width, int height, Image &img
                                   j / af < g_diag_win[1] || j / af >= g_diag_win[3]))
           continue;  // diagnostic window (oracle_set_diag): buf stays black
         Rgb acc;
-        double dx = (double)(2 * (i - xc)) / (double)W;
-        double dy = (double)(2 * (j - yc)) / (double)H;
-        V3 far_point = far_org + (far_right * dx) + (far_up * dy);
         for (int k = 0; k < P.dof_test; k++) {
-          uint64_t psample = ((uint64_t)j * W + i) * (uint64_t)P.dof_test + k;
-          Rng rng(P.seed, KIND_PRIMARY, psample, 0);
-          V3 org = cam.eye;
-          if (P.depth_of_field) {
-            double r1, r2;
-            do {
-              r1 = (rng.next() * 2.0) - 1.0;
-              r2 = (rng.next() * 2.0) - 1.0;
-            } while (r1 * r1 + r2 * r2 > 1.0);
-            org = cam.eye + r1 * u + r2 * v;
-          }
-          V3 dir = normalize(far_point - org);
+          Rng rng;
+          V3 org, dir;
+          uint64_t psample = camera_ray(c, f, i, j, k, rng, org, dir);
           Hit h;
           if (intersect(c, org, dir, h)) {
             Rgb color;
-            ray_trace(c, h, cam.eye, color, rng, psample, cnt);
+            ray_trace(c, h, f.eye, color, rng, psample, cnt);
             acc += color;
             cnt.ray++;
           } else {
@@ -1687,6 +1717,100 @@ int oracle_run_tags(int argc, char **argv, const int *tags, int ntags, float *rg
     if (rgb) memcpy(rgb + (size_t)t * w * h * 3, img.rgb.data(), (size_t)w * h * 3);
   }
   g_tag_select = -100;
+  delete c;
+  return 0;
+}
+
+// The rays and stream ids render_image(aa, w, h) traces (-resolution, -aa and -dof of argv), in
+// gi.h's gi_camera_rays order: output pixels row-major (row 0 = bottom), within a pixel the
+// sub-cells row-major, within a sub-cell the dof_test lens samples. rays: 6 doubles per ray
+// (origin, direction). *n = the ray count; rays == NULL only reports it.
+int oracle_camera_rays(int argc, char **argv, double *rays, uint64_t *ids, int64_t capacity,
+                       int64_t *n) {
+  Ctx *c = new Ctx();
+  std::string out, err;
+  int w, h, aa;
+  if (!setup(*c, argc, argv, out, w, h, aa, err)) {
+    fprintf(stderr, "%s\n", err.c_str());
+    delete c;
+    return 1;
+  }
+  const CamFrame f = cam_frame(*c, aa, w, h);
+  int dof = c->P.dof_test;
+  *n = (int64_t)f.W * f.H * dof;
+  if (!rays) { delete c; return 0; }
+  if (capacity < *n) { delete c; return 2; }
+  int64_t r = 0;
+  for (int y = 0; y < h; y++)
+    for (int x = 0; x < w; x++)
+      for (int sj = 0; sj < f.af; sj++)
+        for (int si = 0; si < f.af; si++)
+          for (int k = 0; k < dof; k++, r++) {
+            Rng rng;
+            V3 org, dir;
+            uint64_t id = camera_ray(*c, f, x * f.af + si, y * f.af + sj, k, rng, org, dir);
+            for (int a = 0; a < 3; a++) {
+              rays[6 * r + a] = org[a];
+              rays[6 * r + 3 + a] = dir[a];
+            }
+            if (ids) ids[r] = id;
+          }
+  delete c;
+  return 0;
+}
+
+// gi.h's gi_render_rays restated: pixel p (row-major, row 0 = bottom; width and height from
+// -resolution) is the mean of rays [p * spp, (p + 1) * spp), each traced as given from stream
+// ids[r] (r when ids is NULL), shaded as seen from its own origin (render.cpp:119-131 with the
+// ray's origin as the eye), clamped, summed in order and weighted by 1.0 / spp (render.cpp:205-
+// 221). -aa and depth of field are ignored. rays: 6 doubles per ray. stats[9] = {screen, shadow,
+// monte, trans, spec, indirect, caustic, knn, knn_photons}. rgb8 / rgbf / stats are optional.
+int oracle_render_rays(int argc, char **argv, int spp, const double *rays, const uint64_t *ids,
+                       uint8_t *rgb8, float *rgbf, double *stats) {
+  if (spp < 1 || !rays) return 4;
+  Ctx *c = new Ctx();
+  std::string out, err;
+  int w, h, aa;
+  if (!setup(*c, argc, argv, out, w, h, aa, err)) {
+    fprintf(stderr, "%s\n", err.c_str());
+    delete c;
+    return 1;
+  }
+  gi_photon_stats pst{};
+  if (c->P.indirect_illum || c->P.caustic_illum || c->P.direct_photon_illum) map_photons(*c, &pst);
+  Counters cnt;
+  double weight = 1.0 / spp;
+  for (int64_t p = 0; p < (int64_t)w * h; p++) {
+    Rgb sum;
+    for (int s = 0; s < spp; s++) {
+      int64_t r = p * spp + s;
+      uint64_t id = ids ? ids[r] : (uint64_t)r;
+      Rng rng(c->P.seed, KIND_PRIMARY, id, 0);
+      V3 org(rays[6 * r], rays[6 * r + 1], rays[6 * r + 2]);
+      V3 dir(rays[6 * r + 3], rays[6 * r + 4], rays[6 * r + 5]);
+      Rgb color;
+      Hit hit;
+      if (intersect(*c, org, dir, hit)) {
+        ray_trace(*c, hit, org, color, rng, id, cnt);
+        cnt.ray++;
+      } else {
+        color = c->scene.background;
+      }
+      clamp_color(color);
+      sum += color;
+    }
+    Rgb col = weight * sum;
+    for (int ch = 0; ch < 3; ch++) {
+      if (rgb8) rgb8[3 * p + ch] = (uint8_t)(255 * col[ch]);
+      if (rgbf) rgbf[3 * p + ch] = (float)col[ch];
+    }
+  }
+  if (stats) {
+    double s[9] = {(double)cnt.ray, (double)cnt.shadow, (double)cnt.monte, (double)cnt.trans,
+                   (double)cnt.spec, (double)cnt.indirect, (double)cnt.caustic, (double)cnt.knn,
+                   (double)cnt.knn_photons};
+    memcpy(stats, s, sizeof s);
+  }
   delete c;
   return 0;
 }

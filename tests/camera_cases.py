@@ -1,5 +1,5 @@
-"""Cases shared by tests/test_gpu_camera.py and tests/test_cli_camera.py: two scenes with a new
-camera each, and the oracle's renders of them (computed once per test session).
+"""Cases shared by tests/test_gpu_camera.py and tests/test_cli_camera.py: scenes with a new
+camera each, and the oracle's renders of them, 8-bit and float (computed once per test session).
 
 The reference for a set camera is the oracle rendering a copy of the scene file whose `camera`
 line is rewritten: the restatement renders any .scn. Both cameras are used at 24 x 16 (not
@@ -23,6 +23,11 @@ CASES = {
                 CORNELL_FLAGS),
     "jensen": ("jensen.scn", "4.2 4.0 -7.0  -0.18 -0.15 1  0.05 1 0  0.36  0.01 100",
                JENSEN_FLAGS),
+    # the cornell case on dimmed_cornell(): 59 % of the cornell view's channel values are 255 and
+    # 13 % are 0 (a unit point light with 1 / d^2 falloff inside a 1.1-wide box), and an error in
+    # a clamped value cannot show
+    "cornell_dim": ("dimmed", "0.95 0.80 -1.2  -0.30 -0.20 1  0.1 1 0.05  0.40  0.01 100",
+                    CORNELL_FLAGS),
 }
 # cornell.scn's own `camera` line: eye, towards, up, xfov
 CORNELL_FILE_CAMERA = ((0.556, 0.546, -1.6), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), 0.329)
@@ -47,18 +52,60 @@ def rewrite_scene(src, camera_line, dst_dir):
     return dst
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_view(name):
-    """(8-bit image, stats) of the oracle on case `name`'s rewritten scene."""
+def tmp_dir():
     global _tmp
     if _tmp is None:
         _tmp = tempfile.TemporaryDirectory(prefix="gi_views_")
-    scn, cam, flags = CASES[name]
-    path = rewrite_scene(scene(scn), cam, _tmp.name)
-    return oracle_lib.render([path, "/tmp/x.png"] + flags, 24, 16)
+    return _tmp.name
+
+
+@functools.lru_cache(maxsize=None)
+def dimmed_cornell():
+    """Copy of cornell.scn (written once per test session) whose point light is 0.2 0.2 0.2
+    instead of 1 1 1, so that most values of a view lie strictly inside (0, 1)."""
+    with open(scene("cornell.scn")) as f:
+        text = f.read()
+    assert text.count("point_light 1 1 1") == 1
+    dst = os.path.join(tmp_dir(), "dim_cornell.scn")
+    with open(dst, "w") as f:
+        f.write(text.replace("point_light 1 1 1", "point_light 0.2 0.2 0.2"))
+    return dst
+
+
+def case_scene(name):
+    """The scene file case `name` starts from (its own camera line still in it)."""
+    scn = CASES[name][0]
+    return dimmed_cornell() if scn == "dimmed" else scene(scn)
+
+
+def _view_args(name):
+    _scn, cam, flags = CASES[name]
+    return [rewrite_scene(case_scene(name), cam, tmp_dir()), "/tmp/x.png"] + flags
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_view(name):
+    """(8-bit image, stats) of the oracle on case `name`'s rewritten scene."""
+    return oracle_lib.render(_view_args(name), 24, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_view_float(name):
+    """The oracle's float image of case `name`'s rewritten scene."""
+    f, rgb = oracle_lib.render_float(_view_args(name), 24, 16)
+    assert (rgb == oracle_view(name)[0]).all()
+    return f
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_file_view():
     """The oracle on cornell.scn as it is (the file's camera), CORNELL_FLAGS."""
     return oracle_lib.render([scene("cornell.scn"), "/tmp/x.png"] + CORNELL_FLAGS, 24, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_file_view_float():
+    """The oracle's float image of cornell.scn as it is, CORNELL_FLAGS."""
+    f, rgb = oracle_lib.render_float([scene("cornell.scn"), "/tmp/x.png"] + CORNELL_FLAGS, 24, 16)
+    assert (rgb == oracle_file_view()[0]).all()
+    return f

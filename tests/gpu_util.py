@@ -68,3 +68,21 @@ def compare(a, b, exact_frac, le1_frac, mean_tol, l2_rms_tol=None):
     tol = l2_rms_tol if l2_rms_tol is not None else L2_RMS_TOL
     if tol is not None:
         assert rms <= tol, (rms, tol)
+
+
+def compare_float_ulp(dev, ref):
+    """Float image parity: every value within one float32 ulp of the oracle's,
+    |dev - ref| <= np.spacing(max(dev, ref)). The device sums a pixel's radiance in fp64 in
+    another order than the oracle, within rtol 1e-10 (the suite's estimate tolerance), 600 times
+    below half a float32 ulp: the rounding to float32 can flip, by one ulp and no more. Returns
+    the number of values that differ at all."""
+    dev = np.asarray(dev, dtype=np.float32)
+    ref = np.asarray(ref, dtype=np.float32)
+    assert dev.shape == ref.shape, (dev.shape, ref.shape)
+    diff = np.abs(dev.astype(np.float64) - ref.astype(np.float64))
+    ulp = np.spacing(np.maximum(dev, ref)).astype(np.float64)
+    ndiff = int((dev != ref).sum())
+    worst = float((diff / ulp).max())
+    print(f"float image: {ndiff} of {dev.size} values differ, worst {worst:.2f} ulp")
+    assert (diff <= ulp).all(), (ndiff, worst, np.argwhere(diff > ulp)[:8].tolist())
+    return ndiff

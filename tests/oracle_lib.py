@@ -180,3 +180,56 @@ def render_float(args, width, height):
     rc = L.oracle_run_tags(n, argv, tags, 1, f.ctypes.data, rgb.ctypes.data, width * height)
     assert rc == 0, rc
     return f, rgb
+
+
+RAY_DTYPE = np.dtype([("org", "<f8", 3), ("dir", "<f8", 3)])  # gi.h's gi_ray
+COUNTER_KEYS = ("screen_rays", "shadow_rays", "monte_carlo_rays", "transmissive_samples",
+                "specular_samples", "indirect_samples", "caustic_samples", "knn_queries",
+                "knn_photons")
+
+
+def camera_rays(args):
+    """The primary rays and RNG stream ids the oracle's render of `args` traces
+    (oracle_camera_rays; -resolution, -aa, -dof): (rays [n] RAY_DTYPE, ids [n] uint64) in
+    gi_camera_rays' order -- output pixels row-major from the bottom row, a pixel's sub-cells
+    row-major, a sub-cell's lens samples."""
+    L = lib()
+    L.oracle_camera_rays.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.POINTER(C.c_int64)]
+    n, argv = _argv(args)
+    cnt = C.c_int64(0)
+    rc = L.oracle_camera_rays(n, argv, None, None, 0, C.byref(cnt))
+    assert rc == 0, rc
+    rays = np.zeros(cnt.value, dtype=RAY_DTYPE)
+    ids = np.zeros(cnt.value, dtype=np.uint64)
+    rc = L.oracle_camera_rays(n, argv, rays.ctypes.data, ids.ctypes.data, cnt.value,
+                              C.byref(cnt))
+    assert rc == 0, rc
+    return rays, ids
+
+
+def render_rays(args, spp, rays, ids=None):
+    """gi_render_rays restated on the CPU (oracle_render_rays): photon maps from `args`, width
+    and height from its -resolution, `spp` rays per pixel, stream ids `ids` (default: the ray's
+    index). Returns (rgb8 [H,W,3], rgbf [H,W,3] float32, the nine render counters), row 0 =
+    bottom."""
+    L = lib()
+    L.oracle_render_rays.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    a = list(args)
+    i = a.index("-resolution")
+    width, height = int(a[i + 1]), int(a[i + 2])
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+    assert len(rays) == width * height * spp, (len(rays), width, height, spp)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        assert len(ids) == len(rays)
+    n, argv = _argv(a)
+    rgb = np.zeros((height, width, 3), dtype=np.uint8)
+    f = np.zeros((height, width, 3), dtype=np.float32)
+    st = np.zeros(9, dtype=np.float64)
+    rc = L.oracle_render_rays(n, argv, spp, rays.ctypes.data,
+                              None if ids is None else ids.ctypes.data, rgb.ctypes.data,
+                              f.ctypes.data, st.ctypes.data)
+    assert rc == 0, rc
+    return rgb, f, dict(zip(COUNTER_KEYS, st.tolist()))

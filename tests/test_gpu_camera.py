@@ -3,7 +3,9 @@ gi_render_rays (gi.h "views from resident photon maps").
 
 - A set camera is checked against the oracle rendering a copy of the scene file whose `camera`
   line is rewritten (the oracle renders any .scn), with the photon maps built once, before the
-  camera changes. The new cameras are non-square (24 x 16) with a non-orthogonal `up`.
+  camera changes. The new cameras are non-square (24 x 16) with a non-orthogonal `up`. The float
+  image is compared too (within one float32 ulp), and one case is a dimmed cornell, whose values
+  are not mostly clamped.
 - A ray batch replayed from the camera's own rays (camera_rays -> render_rays) must return
   RenderImage's float image, 8-bit image and counters bit for bit, across batches, slot-guard
   re-runs and the tile shards of a device set; a permuted or partly replaced batch shows that
@@ -13,9 +15,10 @@ import numpy as np
 import pytest
 
 import gi_amd
-from camera_cases import (CASES, CORNELL_FILE_CAMERA, CORNELL_FLAGS, camera_of, oracle_file_view,
-                          oracle_view)
-from gpu_util import compare_exact, run_gpu, scene
+from camera_cases import (CASES, CORNELL_FILE_CAMERA, CORNELL_FLAGS, camera_of, case_scene,
+                          oracle_file_view, oracle_file_view_float, oracle_view,
+                          oracle_view_float)
+from gpu_util import compare_exact, compare_float_ulp, run_gpu, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +35,11 @@ def cornell_args(flags=CORNELL_FLAGS):
 _one_device = {}
 
 
-@pytest.mark.parametrize("name", ["cornell", "jensen"])
+@pytest.mark.parametrize("name", ["cornell", "jensen", "cornell_dim"])
 def test_set_camera_matches_oracle_on_rewritten_scene(renderer, name):
-    scn, cam, flags = CASES[name]
-    rgb0, _f0, _st0, _pst = run_gpu(renderer, [scene(scn), "/tmp/x.png"] + flags, want_float=True)
+    _scn, cam, flags = CASES[name]
+    rgb0, _f0, _st0, _pst = run_gpu(renderer, [case_scene(name), "/tmp/x.png"] + flags,
+                                    want_float=True)
     maps0 = [renderer.photon_map(m).copy() for m in (gi_amd.GLOBAL, gi_amd.CAUSTIC)]
     renderer.set_camera(*camera_of(cam))
     rgb1, f1, st1 = renderer.RenderImage(0 if name == "jensen" else 1, 24, 16, want_float=True)
@@ -45,6 +49,7 @@ def test_set_camera_matches_oracle_on_rewritten_scene(renderer, name):
     compare_exact(rgb1, ref)
     for k in COUNTERS:
         assert st1[k] == ost[k], k
+    compare_float_ulp(f1, oracle_view_float(name))
     for m, before in zip((gi_amd.GLOBAL, gi_amd.CAUSTIC), maps0):
         np.testing.assert_array_equal(renderer.photon_map(m), before)
     assert (rgb0 != rgb1).any(-1).mean() > 0.5  # the view really changed
@@ -137,6 +142,7 @@ def test_camera_rays_replay_is_exact(renderer):
     compare_exact(rgb1, ref)
     for k in COUNTERS:
         assert st1[k] == ost[k], k
+    compare_float_ulp(f1, oracle_file_view_float())
 
 
 def test_render_rays_argument_checks(renderer):
