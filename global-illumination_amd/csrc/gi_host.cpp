@@ -14,11 +14,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 #include "../../include/gi.h"
+#include "gi_denoise.h"
 #include "gi_kdbuild.h"
 #include "gi_kernels.h"
 #include "gi_scene.h"
@@ -424,6 +426,9 @@ struct gi_ctx {
   double q_per_prim = 0.0;           // largest queries per primary sample seen so far
   double mc_app_rate[2] = {0.0, 0.0};  // per list: largest appends per Monte Carlo path seen
   float sbmin[3] = {0, 0, 0}, sbmax[3] = {1, 1, 1};
+  // feature planes (gi_camera_features / gi_ray_features): one chunk of sample records and of
+  // planes; denoise pass (gi_denoise): the frame's floats, its planes, the two ping-pong images
+  DBuf feat_samples, feat_planes, dn_rgbf, dn_planes, dn_img[2];
 };
 
 static void set_err(gi_ctx *c, const std::string &msg) {
@@ -1872,7 +1877,9 @@ static void release_scratch(gi_ctx *c) {
                   &c->pcounts, &c->poffs, &c->pbuf, &c->pkeys, &c->pcursor, &c->ptmp, &c->pacc,
                   &c->pglob, &c->ind_cont, &c->ind_ncont, &c->mc_cont, &c->mc_ncont,
                   &c->mc_cont2, &c->mc_ncont2, &c->prim_rgb, &c->ind_tab, &c->mc_tab,
-                  &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids};
+                  &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids,
+                  &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
+                  &c->dn_img[1]};
   for (DBuf *b : bufs) b->release();
   std::vector<gi_ray>().swap(c->ray_stage);
   std::vector<uint64_t>().swap(c->id_stage);
@@ -2574,6 +2581,198 @@ int gi_compose_tiles(gi_ctx *c, int w, int h, int tile, int nshards, const void 
 int gi_quantize(int w, int h, const float *rgbf, uint8_t *rgb8) {
   if (!rgbf || !rgb8) return GI_ERR_ARG;
   for (size_t i = 0; i < (size_t)w * h * 3; i++) rgb8[i] = (uint8_t)(255 * (double)rgbf[i]);
+  return GI_OK;
+}
+
+// ---- feature planes and denoise pass (gi_denoise.hip; no reference counterpart) ---------
+int gi_get_materials(gi_ctx *c, gi_material *out, int32_t cap, int32_t *n) {
+  if (!c || !n) return GI_ERR_ARG;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded (gi_read_scene)");
+  const std::vector<DMaterial> &mats = c->scene.mats;
+  *n = (int32_t)mats.size();
+  if (!out) return GI_OK;
+  if (cap < *n) return fail(c, GI_ERR_ARG, "material buffer holds fewer materials than the scene");
+  for (size_t i = 0; i < mats.size(); i++) {
+    const DMaterial &m = mats[i];
+    gi_material &o = out[i];
+    for (int k = 0; k < 3; k++) {
+      o.ka[k] = m.ka[k]; o.kd[k] = m.kd[k]; o.ks[k] = m.ks[k]; o.kt[k] = m.kt[k]; o.e[k] = m.e[k];
+    }
+    o.n = m.n;
+    o.ir = m.ir;
+  }
+  return GI_OK;
+}
+
+// Planes of npix_total pixels of spp samples each, in chunks of whole pixels of at most 2^22
+// samples (one pixel where spp is above that). fill(s0, n) leaves samples [s0, s0 + n) of the
+// frame in c->d_rays.
+static int feature_planes(gi_ctx *c, int64_t npix_total, int64_t spp, gi_pixel_features *out,
+                          const std::function<int(int64_t, int64_t)> &fill) {
+  static_assert(sizeof(gi_pixel_features) == 2 * sizeof(float4), "planes are two float4 per pixel");
+  const int64_t chunk_px = std::min(npix_total, std::max<int64_t>(1, ((int64_t)1 << 22) / spp));
+  HIPCHK(c, c->d_rays.ensure((size_t)(chunk_px * spp) * sizeof(gi_ray)));
+  HIPCHK(c, c->feat_samples.ensure((size_t)(chunk_px * spp) * sizeof(FeatSample)));
+  HIPCHK(c, c->feat_planes.ensure((size_t)chunk_px * sizeof(gi_pixel_features)));
+  FeatureArgs a;
+  memset(&a, 0, sizeof a);
+  a.S = make_view(c);
+  a.spp = (int32_t)spp;
+  a.samples = c->feat_samples.as<FeatSample>();
+  a.planes = c->feat_planes.as<float4>();
+  for (int64_t p0 = 0; p0 < npix_total; p0 += chunk_px) {
+    a.npix = std::min(chunk_px, npix_total - p0);
+    a.nsamp = a.npix * spp;
+    int rc = fill(p0 * spp, a.nsamp);
+    if (rc) return rc;
+    a.rays = c->d_rays.as<gi_ray_dev>();
+    launch_feature_trace(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    launch_feature_reduce(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out + p0, c->feat_planes.p, (size_t)a.npix * sizeof(gi_pixel_features),
+                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GI_OK;
+}
+
+int gi_camera_features(gi_ctx *c, int aa, int w, int h, gi_pixel_features *out) {
+  if (!c) return GI_ERR_ARG;
+  DeviceScope dev(c->device);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!out) return fail(c, GI_ERR_ARG, "null feature buffer");
+  if (aa < 0 || aa > 15 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  const gi_params &P = c->P;
+  const int af = 1 << aa, dof = std::max(1, P.dof_test);
+  const int64_t spp = (int64_t)af * af * dof;
+  if (spp >= ((int64_t)1 << 31)) return fail(c, GI_ERR_ARG, "4^aa * dof_test must be below 2^31");
+  CameraRaysArgs ca;
+  memset(&ca, 0, sizeof ca);
+  ca.cam = make_view(c).cam;
+  ca.seed = P.seed;
+  ca.dof = P.depth_of_field;
+  ca.dof_test = dof;
+  ca.af = af;
+  ca.W = w * af;
+  ca.H = h * af;
+  ca.out_w = w;
+  // the frame's rays from camera_rays_kernel itself: the rays gi_camera_rays exports
+  return feature_planes(c, (int64_t)w * h, spp, out, [&](int64_t s0, int64_t n) -> int {
+    HIPCHK(c, c->d_ray_ids.ensure((size_t)n * 8));
+    ca.rays = c->d_rays.as<gi_ray_dev>();
+    ca.ids = c->d_ray_ids.as<uint64_t>();
+    ca.first = s0;
+    ca.n = n;
+    launch_camera_rays(ca, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return GI_OK;
+  });
+}
+
+int gi_ray_features(gi_ctx *c, int w, int h, int spp, const gi_ray *rays, gi_pixel_features *out) {
+  if (!c) return GI_ERR_ARG;
+  DeviceScope dev(c->device);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!rays) return fail(c, GI_ERR_ARG, "null ray buffer");
+  if (!out) return fail(c, GI_ERR_ARG, "null feature buffer");
+  if (spp < 1) return fail(c, GI_ERR_ARG, "spp must be at least 1");
+  if (w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  if ((int64_t)w * h >= ((int64_t)1 << 31) / spp + (((int64_t)1 << 31) % spp != 0))
+    return fail(c, GI_ERR_ARG, "width * height * spp must be below 2^31");
+  return feature_planes(c, (int64_t)w * h, spp, out, [&](int64_t s0, int64_t n) -> int {
+    HIPCHK(c, hipMemcpyAsync(c->d_rays.p, rays + s0, (size_t)n * sizeof(gi_ray),
+                             hipMemcpyHostToDevice, c->stream));
+    return GI_OK;
+  });
+}
+
+void gi_denoise_params_default(gi_denoise_params *p) {
+  if (!p) return;
+  p->levels = 5;
+  p->normal_power_log2 = 5;
+  p->sigma_color = 1.0;
+  p->sigma_depth = 0.05;
+  p->sigma_albedo = 0.1;
+}
+
+int gi_denoise(gi_ctx *c, int w, int h, const float *rgbf, const gi_pixel_features *feat,
+               const gi_denoise_params *pp, float *out_rgbf, uint8_t *out_rgb8, double *kernel_ms) {
+  if (!c) return GI_ERR_ARG;
+  if (!rgbf || !feat || (!out_rgbf && !out_rgb8)) return fail(c, GI_ERR_ARG, "null image buffer");
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(c, GI_ERR_ARG, "bad image size");
+  gi_denoise_params P;
+  gi_denoise_params_default(&P);
+  if (pp) P = *pp;
+  if (P.levels < 1 || P.levels > 8) return fail(c, GI_ERR_ARG, "denoise: levels outside 1..8");
+  if (P.normal_power_log2 < 0 || P.normal_power_log2 > 8)
+    return fail(c, GI_ERR_ARG, "denoise: normal_power_log2 outside 0..8");
+  for (double s : {P.sigma_color, P.sigma_depth, P.sigma_albedo})
+    if (!std::isfinite(s) || !(s > 0.0))
+      return fail(c, GI_ERR_ARG, "denoise: sigmas must be finite and positive");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)w * h;
+  HIPCHK(c, upload(c->dn_rgbf, rgbf, npix * 12, c->stream));
+  HIPCHK(c, upload(c->dn_planes, feat, npix * sizeof(gi_pixel_features), c->stream));
+  HIPCHK(c, c->dn_img[0].ensure(npix * sizeof(float4)));
+  HIPCHK(c, c->dn_img[1].ensure(npix * sizeof(float4)));
+  launch_denoise_pack(c->dn_rgbf.as<float>(), (int64_t)npix, c->dn_img[0].as<float4>(), c->stream);
+  HIPCHK(c, hipGetLastError());
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+      hipEventDestroy(e0);
+      return fail(c, GI_ERR_HIP, "denoise: hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, c->stream);
+  }
+  DenoiseArgs a;
+  memset(&a, 0, sizeof a);
+  a.W = w;
+  a.H = h;
+  a.npow = P.normal_power_log2;
+  a.sigma_depth = P.sigma_depth;
+  a.sa2 = P.sigma_albedo * P.sigma_albedo;
+  a.planes = c->dn_planes.as<float4>();
+  int cur = 0;
+  hipError_t le = hipSuccess;
+  for (int l = 0; l < P.levels && le == hipSuccess; l++) {
+    const double sc = P.sigma_color / (double)(1 << l);
+    a.step = 1 << l;
+    a.sc2 = sc * sc;
+    a.src = c->dn_img[cur].as<float4>();
+    a.dst = c->dn_img[cur ^ 1].as<float4>();
+    launch_denoise_level(a, c->stream);
+    le = hipGetLastError();
+    cur ^= 1;
+  }
+  if (kernel_ms) (void)hipEventRecord(e1, c->stream);
+  if (le == hipSuccess) {
+    launch_denoise_unpack(c->dn_img[cur].as<float4>(), (int64_t)npix, c->dn_rgbf.as<float>(), c->stream);
+    le = hipGetLastError();
+  }
+  std::vector<float> stage;
+  float *dst = out_rgbf;
+  if (!dst) {
+    stage.resize(npix * 3);
+    dst = stage.data();
+  }
+  if (le == hipSuccess)
+    le = hipMemcpyAsync(dst, c->dn_rgbf.p, npix * 12, hipMemcpyDeviceToHost, c->stream);
+  if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
+  if (kernel_ms) {
+    float ms = 0.f;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    *kernel_ms = ms;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  HIPCHK(c, le);
+  if (out_rgb8) return gi_quantize(w, h, dst, out_rgb8);
   return GI_OK;
 }
 

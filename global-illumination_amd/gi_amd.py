@@ -7,6 +7,9 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
   RenderImage      render.cpp:155-259
   get_camera / set_camera / camera_rays / render_rays: further views from the resident photon
                    maps (no reference counterpart; gi.h "views from resident photon maps")
+  materials / camera_features / ray_features / denoise: per-pixel feature planes and the
+                   edge-avoiding denoise pass (no reference counterpart; gi.h "feature planes
+                   and denoise pass")
   EstimateRadiance utils/photon_utils.cpp:72-162      (batched test seam)
   FindClosestQuick R3Shapes/R3Kdtree.cpp:688-848      (batched test seam)
   Intersects       R3Graphics/R3Scene.cpp:471-479     (batched test seam)
@@ -33,6 +36,8 @@ EXPORTED = [
     "gi_get_photon_map", "gi_get_kd_tree", "gi_set_progress", "gi_render_image", "gi_render_tiles",
     "gi_get_camera", "gi_set_camera", "gi_camera_rays", "gi_render_rays",
     "gi_render_tiles_packed", "gi_compose_tiles", "gi_quantize",
+    "gi_get_materials", "gi_camera_features", "gi_ray_features", "gi_denoise_params_default",
+    "gi_denoise",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image",
@@ -71,6 +76,21 @@ class Camera(C.Structure):
 
 RAY_DTYPE = np.dtype([("org", "<f8", 3), ("dir", "<f8", 3)])  # gi_ray
 assert RAY_DTYPE.itemsize == 48
+
+# gi_material / gi_pixel_features
+MATERIAL_DTYPE = np.dtype([("ka", "<f8", 3), ("kd", "<f8", 3), ("ks", "<f8", 3), ("kt", "<f8", 3),
+                           ("e", "<f8", 3), ("n", "<f8"), ("ir", "<f8")])
+assert MATERIAL_DTYPE.itemsize == 136
+FEATURE_DTYPE = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("albedo", "<f4", 3),
+                          ("coverage", "<f4")])
+assert FEATURE_DTYPE.itemsize == 32
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_color", C.c_double), ("sigma_depth", C.c_double),
+                ("sigma_albedo", C.c_double)]
+
 
 GI_MAX_DEVICES = 64
 
@@ -166,6 +186,14 @@ def lib():
         L.gi_compose_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.gi_quantize.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gi_get_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, P(C.c_int32)]
+        L.gi_camera_features.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.gi_ray_features.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]
+        L.gi_denoise_params_default.argtypes = [P(DenoiseParams)]
+        L.gi_denoise_params_default.restype = None
+        L.gi_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 P(DenoiseParams), C.c_void_p, C.c_void_p, P(C.c_double)]
         L.gi_estimate_radiance_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         L.gi_knn_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
@@ -187,6 +215,12 @@ def lib():
 def default_params():
     p = GiParams()
     lib().gi_params_default(C.byref(p))
+    return p
+
+
+def default_denoise_params():
+    p = DenoiseParams()
+    lib().gi_denoise_params_default(C.byref(p))
     return p
 
 
@@ -356,6 +390,55 @@ class Renderer:
                                          rgbf.ctypes.data if want_float else None, C.byref(st)))
         stats = _stats_dict(st)
         return (rgb, rgbf, stats) if want_float else (rgb, stats)
+
+    def materials(self):
+        """The scene's materials as the device holds them, indexed by Intersects' material
+        value (gi_get_materials): [n] MATERIAL_DTYPE."""
+        n = C.c_int32(0)
+        self._check(lib().gi_get_materials(self._ctx, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=MATERIAL_DTYPE)
+        self._check(lib().gi_get_materials(self._ctx, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def camera_features(self, aa, width, height):
+        """Feature planes of the frame RenderImage(aa, width, height) renders
+        (gi_camera_features): [height, width] FEATURE_DTYPE, row 0 = bottom."""
+        out = np.zeros((height, width), dtype=FEATURE_DTYPE)
+        self._check(lib().gi_camera_features(self._ctx, aa, width, height, out.ctypes.data))
+        return out
+
+    def ray_features(self, width, height, spp, rays):
+        """Feature planes of a caller-made ray batch, spp rays per pixel as in render_rays
+        (gi_ray_features): [height, width] FEATURE_DTYPE."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+        need = width * height * spp
+        if spp >= 1 and len(rays) != need:
+            raise ValueError(f"{need} rays expected (width * height * spp), got {len(rays)}")
+        out = np.zeros((height, width), dtype=FEATURE_DTYPE)
+        self._check(lib().gi_ray_features(self._ctx, width, height, spp, rays.ctypes.data,
+                                          out.ctypes.data))
+        return out
+
+    def denoise(self, rgbf, feat, want_float=False, **params):
+        """Edge-avoiding a-trous filter of a float frame [H, W, 3] by its planes [H, W]
+        (gi_denoise); params: fields of gi_denoise_params that differ from the defaults.
+        Returns (rgb8, kernel_ms), or (rgb8, rgbf, kernel_ms) with want_float."""
+        rgbf = np.ascontiguousarray(rgbf, dtype=np.float32)
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        h, w = feat.shape
+        if rgbf.shape != (h, w, 3):
+            raise ValueError(f"image {rgbf.shape} does not match planes {feat.shape}")
+        p = default_denoise_params()
+        for k, v in params.items():
+            if k not in dict(DenoiseParams._fields_):
+                raise TypeError(f"unknown denoise parameter {k}")
+            setattr(p, k, v)
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._check(lib().gi_denoise(self._ctx, w, h, rgbf.ctypes.data, feat.ctypes.data,
+                                     C.byref(p), out.ctypes.data, rgb.ctypes.data, C.byref(ms)))
+        return (rgb, out, ms.value) if want_float else (rgb, ms.value)
 
     def render_tiles(self, aa, width, height, tile, shard, nshards, rgbf=None):
         if rgbf is None:

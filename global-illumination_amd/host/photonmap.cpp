@@ -6,6 +6,8 @@
 // render.cpp:224-255. Exit codes: 1 for a bad flag, -1 (255) for load/render/write failures.
 // Extension: -camera ex ey ez tx ty tz ux uy uz xfov renders from that camera instead of the
 // scene file's (gi_set_camera; the numbers of the .scn `camera` command).
+// Extension: -denoise L writes the frame filtered by L (1..8) levels of the edge-avoiding
+// a-trous pass over its feature planes (gi_camera_features + gi_denoise, default parameters).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,11 +60,32 @@ static bool TakeCamera(int &argc, char **argv, gi_camera &cam, bool &have) {
   return true;
 }
 
+// Takes `-denoise L` out of argv in the same way; false on a missing, non-integer or
+// out-of-range (1..8) L. The last -denoise wins.
+static bool TakeDenoise(int &argc, char **argv, int &levels) {
+  for (int a = 1; a < argc;) {
+    if (strcmp(argv[a], "-denoise")) { a++; continue; }
+    if (a + 1 >= argc) return false;
+    char *end = nullptr;
+    const long v = strtol(argv[a + 1], &end, 10);
+    if (end == argv[a + 1] || *end || v < 1 || v > 8) return false;
+    levels = (int)v;
+    for (int k = a + 2; k < argc; k++) argv[k - 2] = argv[k];
+    argc -= 2;
+  }
+  return true;
+}
+
 int main(int argc, char **argv) {
   gi_camera cam;
   bool have_cam = false;
   if (!TakeCamera(argc, argv, cam, have_cam)) {
     fprintf(stderr, "Invalid program argument: -camera");
+    return 1;
+  }
+  int denoise_levels = 0;  // 0: no denoise pass
+  if (!TakeDenoise(argc, argv, denoise_levels)) {
+    fprintf(stderr, "Invalid program argument: -denoise");
     return 1;
   }
   gi_params P;
@@ -150,10 +173,24 @@ int main(int argc, char **argv) {
   std::vector<uint8_t> rgb((size_t)w * h * 3);
   gi_render_stats rs;
   if (P.verbose) printf("Rendering image ...\n");
-  if (gi_render_image(ctx, aa, w, h, rgb.data(), nullptr, &rs) != GI_OK) {
+  std::vector<float> rgbf(denoise_levels ? (size_t)w * h * 3 : 0);
+  if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
     fprintf(stderr, "%s\n", gi_last_error(ctx));
     gi_destroy(ctx);
     return -1;
+  }
+  double denoise_ms = 0.0;
+  if (denoise_levels) {  // the written image is the filtered frame
+    std::vector<gi_pixel_features> feat((size_t)w * h);
+    gi_denoise_params dp;
+    gi_denoise_params_default(&dp);
+    dp.levels = denoise_levels;
+    if (gi_camera_features(ctx, aa, w, h, feat.data()) != GI_OK ||
+        gi_denoise(ctx, w, h, rgbf.data(), feat.data(), &dp, nullptr, rgb.data(), &denoise_ms) != GI_OK) {
+      fprintf(stderr, "%s\n", gi_last_error(ctx));
+      gi_destroy(ctx);
+      return -1;
+    }
   }
   PrintProgress(1.0, PROGRESS_BAR_WIDTH);  // render.cpp:201-202
   printf("\n");
@@ -170,6 +207,7 @@ int main(int argc, char **argv) {
     if (P.indirect_illum) { printf("  # Indirect Samples = %llu\n", (unsigned long long)rs.indirect_samples); total += rs.indirect_samples; }
     if (P.caustic_illum) { printf("  # Caustic Samples = %llu\n", (unsigned long long)rs.caustic_samples); total += rs.caustic_samples; }
     printf("Total Rays: %llu\n", total);
+    if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);
     fflush(stdout);
   }
   gi_destroy(ctx);

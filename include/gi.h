@@ -287,6 +287,54 @@ int gi_render_rays(gi_ctx *ctx, int width, int height, int spp,
 /* Quantise a full float image like RenderImage's SetPixelRGB (truncate 255*c). */
 int gi_quantize(int width, int height, const float *rgbf, uint8_t *rgb8);
 
+/* ---- feature planes and denoise pass -------------------------------------------------- */
+/* Per-pixel geometry planes of a frame and an edge-avoiding a-trous filter guided by them
+ * (DESIGN.md "Feature planes and denoise pass"). No reference counterpart: the reference
+ * writes the noisy frame only. On a device set these calls run on devices[0], as the test
+ * seams do. */
+typedef struct gi_material { double ka[3], kd[3], ks[3], kt[3], e[3], n, ir; } gi_material;
+/* The scene's materials as the device holds them (after -real normalisation), indexed by the
+ * `material` value gi_intersect_batch returns. *n = their number; out == NULL only reports it,
+ * capacity < *n is GI_ERR_ARG. GI_ERR_STATE before a scene is read. No reference counterpart. */
+int gi_get_materials(gi_ctx *ctx, gi_material *out, int32_t capacity, int32_t *n);
+
+typedef struct gi_pixel_features {      /* 32 bytes */
+  float normal[3]; float depth; float albedo[3]; float coverage;
+} gi_pixel_features;
+/* Planes of the frame gi_render_image(aa, width, height) renders: same primary rays as
+ * gi_camera_rays (lens-sampled under -dof), output pixels row-major, row 0 = bottom. Of a
+ * pixel's S samples, over those that hit, in sample order, in fp64, each value rounded to
+ * float32 once: coverage = hits / S, normal = mean hit normal (as gi_intersect_batch returns
+ * it: not flipped towards the viewer, not renormalised), depth = mean distance origin -> hit,
+ * albedo = mean kd of the hit material; all 0 when no sample hits. Needs a scene, not the
+ * photon maps (GI_ERR_STATE before gi_read_scene). No reference counterpart. */
+int gi_camera_features(gi_ctx *ctx, int aa, int width, int height, gi_pixel_features *out);
+/* ... and of a caller-made ray batch, pixel p = rays [p*spp, (p+1)*spp) as in gi_render_rays.
+ * GI_ERR_ARG for spp < 1, null buffers or width * height * spp >= 2^31. No reference
+ * counterpart. */
+int gi_ray_features(gi_ctx *ctx, int width, int height, int spp, const gi_ray *rays,
+                    gi_pixel_features *out);
+
+typedef struct gi_denoise_params {
+  int32_t levels;             /* 1..8 a-trous levels, step 2^l            default 5    */
+  int32_t normal_power_log2;  /* 0..8: normal weight = max(0,n.n)^(2^e)   default 5    */
+  double sigma_color;         /* halved at every level                    default 1.0  */
+  double sigma_depth;         /* relative depth difference                default 0.05 */
+  double sigma_albedo;        /*                                          default 0.1  */
+} gi_denoise_params;
+void gi_denoise_params_default(gi_denoise_params *p);
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; Lorentzian stopping functions, so
+ * that every operation is exactly rounded) of a frame by its planes. rgbf: W*H*3 floats as
+ * gi_render_image / gi_render_rays return them; feat: the frame's W*H planes (depth > 0 where
+ * coverage > 0). out_rgbf (W*H*3 floats) and out_rgb8 = gi_quantize of out_rgbf: either may
+ * be NULL, not both. p == NULL: defaults. kernel_ms (optional): summed HIP-event time of the
+ * filter launches. GI_ERR_ARG for null buffers, width or height < 1, width * height >= 2^31,
+ * levels or normal_power_log2 out of range, or a sigma that is not finite and positive. Needs
+ * only a context (no scene). Runs on the context's first device. No reference counterpart. */
+int gi_denoise(gi_ctx *ctx, int width, int height, const float *rgbf,
+               const gi_pixel_features *feat, const gi_denoise_params *p,
+               float *out_rgbf, uint8_t *out_rgb8, double *kernel_ms);
+
 /* ---- test seams ----------------------------------------------------------------------- */
 /* n <= 2^26 queries per call (GI_ERR_ARG above). */
 int gi_estimate_radiance_batch(gi_ctx *ctx, int map, int64_t n, const gi_radiance_query *q,
