@@ -21,6 +21,7 @@
 #include <vector>
 #include "../../include/gi.h"
 #include "gi_denoise.h"
+#include "gi_radiance.h"
 #include "gi_kdbuild.h"
 #include "gi_kernels.h"
 #include "gi_scene.h"
@@ -429,6 +430,18 @@ struct gi_ctx {
   // feature planes (gi_camera_features / gi_ray_features): one chunk of sample records and of
   // planes; denoise pass (gi_denoise): the frame's floats, its planes, the two ping-pong images
   DBuf feat_samples, feat_planes, dn_rgbf, dn_planes, dn_img[2];
+  // radiance frames (gi_render_radiance, gi_render_rays_radiance, gi_accum_add_*): while rad_on,
+  // render_pixels launches reduce_radiance_kernel beside reduce_kernel; rad_frame holds the pass's
+  // {m, M2} (six doubles per pixel), rad_samples the samples when the caller asked for them
+  bool rad_on = false, rad_want_samples = false;
+  DBuf rad_frame, rad_samples, rad_mean, rad_var;
+  // accumulator over passes (gi_accum_*): {mu, A} per pixel and one sample count for the frame;
+  // state of the context, kept by gi_release_scratch
+  DBuf acc, acc_part;
+  int acc_w = 0, acc_h = 0;
+  int64_t acc_n = 0;
+  bool acc_valid = false;
+  DBuf tm_in, tm_out;             // gi_tonemap
 };
 
 static void set_err(gi_ctx *c, const std::string &msg) {
@@ -1652,6 +1665,21 @@ int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &p
     a.prim_rgb = c->prim_rgb.as<double>();
     launch_reduce(a, c->stream);
     HIPCHK(c, hipGetLastError());
+    if (c->rad_on) {  // the same primaries once more, unclamped (gi_radiance.hip)
+      RadianceArgs ra;
+      memset(&ra, 0, sizeof ra);
+      ra.prim_rgb = a.prim_rgb;
+      ra.pixels = a.pixels;
+      ra.npix = a.npix;
+      ra.S = a.spp ? a.spp : a.af * a.af;
+      ra.dof_test = a.dof_test;
+      ra.out_w = a.out_w;
+      ra.bw = a.spp ? 1.0 / a.spp : 1.0 / a.af / a.af;
+      ra.frame = c->rad_frame.as<double>();
+      ra.samples = c->rad_want_samples ? c->rad_samples.as<double>() : nullptr;
+      launch_reduce_radiance(ra, c->stream);
+      HIPCHK(c, hipGetLastError());
+    }
     if (c->progress) c->progress(0, (double)(p0 + npix) / (double)npix_total, c->progress_user);
     if (c->batch_log) {  // GI_LOG & 2: one stderr line per batch (synchronises the batch)
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1879,7 +1907,8 @@ static void release_scratch(gi_ctx *c) {
                   &c->mc_cont2, &c->mc_ncont2, &c->prim_rgb, &c->ind_tab, &c->mc_tab,
                   &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids,
                   &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
-                  &c->dn_img[1]};
+                  &c->dn_img[1], &c->rad_frame, &c->rad_samples, &c->rad_mean, &c->rad_var,
+                  &c->acc_part, &c->tm_in, &c->tm_out};
   for (DBuf *b : bufs) b->release();
   std::vector<gi_ray>().swap(c->ray_stage);
   std::vector<uint64_t>().swap(c->id_stage);
@@ -1927,7 +1956,7 @@ void gi_destroy(gi_ctx *c) {
   hipSetDevice(c->device);
   release_scratch(c);
   DBuf *bufs[] = {&c->d_nodes, &c->d_elems, &c->d_shapes, &c->d_tris, &c->d_bvh, &c->d_mats,
-                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount};
+                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount, &c->acc};
   for (DBuf *b : bufs) b->release();
   for (int m = 0; m < 2; m++) {
     MapExec &X = c->mx[m];
@@ -2773,6 +2802,303 @@ int gi_denoise(gi_ctx *c, int w, int h, const float *rgbf, const gi_pixel_featur
   }
   HIPCHK(c, le);
   if (out_rgb8) return gi_quantize(w, h, dst, out_rgb8);
+  return GI_OK;
+}
+
+// ---- radiance frames, accumulator and tone map (gi_radiance.hip; no reference counterpart) ----
+// One render with the radiance reduction on: c->rad_frame then holds the finished pass {m, M2}
+// (written once per pixel by the render that completed: a re-render after ST_GEN_MISS overwrites
+// every pixel, a batch re-run under the slot guard never reached its reduction).
+static int radiance_pass(gi_ctx *c, int aa, int w, int h, bool want_samples, gi_render_stats *st,
+                         const RaySrc *rsrc, int64_t *S_out) {
+  hipSetDevice(c->device);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (aa < 0 || aa > 15 || w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  const int64_t S = rsrc ? (int64_t)rsrc->spp : (int64_t)1 << (2 * aa);
+  const size_t npix = (size_t)w * h;
+  if ((int64_t)npix >= ((int64_t)1 << 31) / S + (((int64_t)1 << 31) % S != 0))
+    return fail(c, GI_ERR_ARG, "width * height * samples per pixel must be below 2^31");
+  HIPCHK(c, c->rad_frame.ensure(npix * 48));
+  if (want_samples) HIPCHK(c, c->rad_samples.ensure(npix * (size_t)S * 24));
+  c->rad_want_samples = want_samples;
+  c->rad_on = true;
+  rc = render_frame(c, aa, w, h, nullptr, nullptr, st, rsrc);
+  c->rad_on = false;
+  *S_out = S;
+  return rc;
+}
+
+// {m, M2} of n samples per pixel -> host float mean / variance of the mean (either may be null)
+static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n, float *mean,
+                            float *variance) {
+  if (!mean && !variance) return GI_OK;
+  HIPCHK(c, c->rad_mean.ensure(npix * 12));
+  HIPCHK(c, c->rad_var.ensure(npix * 12));
+  ResolveArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = (int64_t)npix;
+  a.n = n;
+  a.frame = (const double *)frame.p;
+  a.mean = mean ? c->rad_mean.as<float>() : nullptr;
+  a.variance = variance ? c->rad_var.as<float>() : nullptr;
+  launch_radiance_resolve(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  if (mean) HIPCHK(c, hipMemcpyAsync(mean, c->rad_mean.p, npix * 12, hipMemcpyDeviceToHost, c->stream));
+  if (variance)
+    HIPCHK(c, hipMemcpyAsync(variance, c->rad_var.p, npix * 12, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+static int render_radiance(gi_ctx *c, int aa, int w, int h, const RaySrc *rsrc, float *mean,
+                           float *variance, double *samples, gi_render_stats *st) {
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "radiance frames are for one-device contexts");
+  if (!mean && !variance && !samples) return fail(c, GI_ERR_ARG, "null image buffer");
+  int64_t S = 0;
+  int rc = radiance_pass(c, aa, w, h, samples != nullptr, st, rsrc, &S);
+  if (rc) return rc;
+  const size_t npix = (size_t)w * h;
+  if (samples) {
+    HIPCHK(c, hipMemcpyAsync(samples, c->rad_samples.p, npix * (size_t)S * 24, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return radiance_resolve(c, c->rad_frame, npix, S, mean, variance);
+}
+
+// gi_render_rays' argument checks
+static int check_ray_args(gi_ctx *c, int w, int h, int spp, const gi_ray *rays) {
+  if (!rays) return fail(c, GI_ERR_ARG, "null ray buffer");
+  if (spp < 1) return fail(c, GI_ERR_ARG, "spp must be at least 1");
+  if (w <= 0 || h <= 0) return fail(c, GI_ERR_ARG, "bad image size");
+  if ((int64_t)w * h >= ((int64_t)1 << 31) / spp + (((int64_t)1 << 31) % spp != 0))
+    return fail(c, GI_ERR_ARG, "width * height * spp must be below 2^31");
+  return GI_OK;
+}
+
+int gi_render_radiance(gi_ctx *c, int aa, int w, int h, float *mean, float *variance,
+                       double *samples, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  return render_radiance(c, aa, w, h, nullptr, mean, variance, samples, st);
+}
+
+int gi_render_rays_radiance(gi_ctx *c, int w, int h, int spp, const gi_ray *rays,
+                            const uint64_t *ids, float *mean, float *variance, double *samples,
+                            gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "radiance frames are for one-device contexts");
+  int rc = check_ray_args(c, w, h, spp, rays);
+  if (rc) return rc;
+  const RaySrc src{rays, ids, spp};
+  return render_radiance(c, 0, w, h, &src, mean, variance, samples, st);
+}
+
+int gi_accum_reset(gi_ctx *c, int w, int h) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(c, GI_ERR_ARG, "bad image size");
+  DeviceScope dev(c->device);
+  c->acc_valid = false;
+  const size_t npix = (size_t)w * h;
+  HIPCHK(c, c->acc.ensure(npix * 48));
+  HIPCHK(c, hipMemsetAsync(c->acc.p, 0, npix * 48, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->acc_w = w;
+  c->acc_h = h;
+  c->acc_n = 0;
+  c->acc_valid = true;
+  return GI_OK;
+}
+
+// one finished pass (c->rad_frame, S samples per pixel) into the accumulator
+static int accum_pass(gi_ctx *c, int aa, const RaySrc *rsrc, gi_render_stats *st) {
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
+  int64_t S = 0;
+  int rc = radiance_pass(c, aa, c->acc_w, c->acc_h, false, st, rsrc, &S);
+  if (rc) return rc;
+  AccumArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = (int64_t)c->acc_w * c->acc_h;
+  a.N = c->acc_n;
+  a.S = S;
+  a.pass = c->rad_frame.as<double>();
+  a.acc = c->acc.as<double>();
+  launch_accum_merge(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->acc_n += S;
+  return GI_OK;
+}
+
+int gi_accum_add_image(gi_ctx *c, int aa, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  return accum_pass(c, aa, nullptr, st);
+}
+
+int gi_accum_add_rays(gi_ctx *c, int spp, const gi_ray *rays, const uint64_t *ids,
+                      gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
+  int rc = check_ray_args(c, c->acc_w, c->acc_h, spp, rays);
+  if (rc) return rc;
+  const RaySrc src{rays, ids, spp};
+  return accum_pass(c, 0, &src, st);
+}
+
+int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, double *noise) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  if (nsamples) *nsamples = c->acc_n;
+  int rc = radiance_resolve(c, c->acc, npix, c->acc_n, mean, variance);
+  if (rc || !noise) return rc;
+  const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
+  HIPCHK(c, c->acc_part.ensure(nb * 8));
+  NoiseArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = (int64_t)npix;
+  a.n = c->acc_n;
+  a.acc = c->acc.as<double>();
+  a.partial = c->acc_part.as<double>();
+  launch_accum_noise(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  std::vector<double> part(nb);
+  HIPCHK(c, hipMemcpyAsync(part.data(), c->acc_part.p, nb * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  double sum = 0.0;
+  for (double v : part) sum += v;  // in block order: the result is reproducible bit for bit
+  *noise = sum / (double)npix;
+  return GI_OK;
+}
+
+int gi_tonemap(gi_ctx *c, int w, int h, const float *radiance, double exposure, double white,
+               float *out_rgbf, uint8_t *out_rgb8) {
+  if (!c) return GI_ERR_ARG;
+  if (!radiance || (!out_rgbf && !out_rgb8)) return fail(c, GI_ERR_ARG, "null image buffer");
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(c, GI_ERR_ARG, "bad image size");
+  if (!std::isfinite(exposure) || !(exposure > 0.0))
+    return fail(c, GI_ERR_ARG, "tonemap: exposure must be finite and positive");
+  if (!std::isfinite(white) || white < 0.0)
+    return fail(c, GI_ERR_ARG, "tonemap: white must be finite and not negative");
+  DeviceScope dev(c->device);
+  const size_t nval = (size_t)w * h * 3;
+  HIPCHK(c, upload(c->tm_in, radiance, nval * 4, c->stream));
+  HIPCHK(c, c->tm_out.ensure(nval * 4));
+  TonemapArgs a;
+  memset(&a, 0, sizeof a);
+  a.nval = (int64_t)nval;
+  a.exposure = exposure;
+  a.white = white;
+  a.in = c->tm_in.as<float>();
+  a.out = c->tm_out.as<float>();
+  launch_tonemap(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  std::vector<float> stage;
+  float *dst = out_rgbf;
+  if (!dst) {
+    stage.resize(nval);
+    dst = stage.data();
+  }
+  HIPCHK(c, hipMemcpyAsync(dst, c->tm_out.p, nval * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (out_rgb8) return gi_quantize(w, h, dst, out_rgb8);
+  return GI_OK;
+}
+
+// Diagnostics: the three kernels on a synthetic frame (every primary sum the same finite value:
+// none of them branches on data), each launch between two HIP events. Buffers of its own, freed
+// on return: the context's accumulator is untouched.
+int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, double *reduce_ms,
+                      double *merge_ms, double *noise_ms) {
+  if (!c) return GI_ERR_ARG;
+  if (aa < 0 || aa > 15 || w <= 0 || h <= 0 || warmup < 0 || reps < 1 || reps > 10000)
+    return fail(c, GI_ERR_ARG, "radiance bench: bad size or repetition count");
+  const int64_t S = (int64_t)1 << (2 * aa);
+  const size_t npix = (size_t)w * h;
+  if ((int64_t)npix >= ((int64_t)1 << 31) / S) return fail(c, GI_ERR_ARG, "radiance bench: frame too large");
+  DeviceScope dev(c->device);
+  std::vector<int32_t> pix(npix * 2);
+  for (size_t p = 0; p < npix; p++) {
+    pix[2 * p] = (int32_t)(p % w);
+    pix[2 * p + 1] = (int32_t)(p / w);
+  }
+  DBuf prim, pixels, frame, acc, part;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
+  auto run = [&]() -> hipError_t {
+    hipError_t e;
+    if ((e = prim.ensure(npix * (size_t)S * 24)) != hipSuccess) return e;
+    if ((e = upload(pixels, pix.data(), pix.size() * 4, c->stream)) != hipSuccess) return e;
+    if ((e = frame.ensure(npix * 48)) != hipSuccess) return e;
+    if ((e = acc.ensure(npix * 48)) != hipSuccess) return e;
+    if ((e = part.ensure(nb * 8)) != hipSuccess) return e;
+    // bytes 0x3f: every double is 4.7e-4
+    if ((e = hipMemsetAsync(prim.p, 0x3f, npix * (size_t)S * 24, c->stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(acc.p, 0, npix * 48, c->stream)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&e0)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&e1)) != hipSuccess) return e;
+    RadianceArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.prim_rgb = prim.as<double>();
+    ra.pixels = pixels.as<int2>();
+    ra.npix = (int32_t)npix;
+    ra.S = (int32_t)S;
+    ra.dof_test = 1;
+    ra.out_w = w;
+    ra.bw = 1.0 / (1 << aa) / (1 << aa);
+    ra.frame = frame.as<double>();
+    AccumArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.npix = (int64_t)npix;
+    ma.N = S;  // the general branch
+    ma.S = S;
+    ma.pass = frame.as<double>();
+    ma.acc = acc.as<double>();
+    NoiseArgs na;
+    memset(&na, 0, sizeof na);
+    na.npix = (int64_t)npix;
+    na.n = 2 * S;
+    na.acc = acc.as<double>();
+    na.partial = part.as<double>();
+    double *out[3] = {reduce_ms, merge_ms, noise_ms};
+    for (int k = 0; k < 3; k++) {
+      std::vector<float> ms;
+      for (int i = 0; i < warmup + reps; i++) {
+        if ((e = hipEventRecord(e0, c->stream)) != hipSuccess) return e;
+        if (k == 0) launch_reduce_radiance(ra, c->stream);
+        else if (k == 1) launch_accum_merge(ma, c->stream);
+        else launch_accum_noise(na, c->stream);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(e1, c->stream)) != hipSuccess) return e;
+        if ((e = hipEventSynchronize(e1)) != hipSuccess) return e;
+        float t = 0.f;
+        if ((e = hipEventElapsedTime(&t, e0, e1)) != hipSuccess) return e;
+        if (i >= warmup) ms.push_back(t);
+      }
+      std::sort(ms.begin(), ms.end());
+      if (out[k]) *out[k] = ms.size() % 2 ? ms[ms.size() / 2] : 0.5 * (ms[ms.size() / 2 - 1] + ms[ms.size() / 2]);
+    }
+    return hipSuccess;
+  };
+  const hipError_t e = run();
+  (void)hipStreamSynchronize(c->stream);
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  for (DBuf *b : {&prim, &pixels, &frame, &acc, &part}) b->release();
+  HIPCHK(c, e);
   return GI_OK;
 }
 

@@ -12,6 +12,7 @@
 //   .raw        R2Image::WriteRAW  (:1545-1604)  {54321, w, h, 3} header + planar f32 / 255
 //   .tif/.tiff  the reference is built without RN_USE_TIFF: "TIFF not supported" -> error
 #include <zlib.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -452,6 +453,57 @@ int gi_write_image(const char *path, int w, int h, const uint8_t *rgb) {
     compress2(z.data(), &zl, raw.data(), raw.size(), 6);
     chunk("IDAT", z.data(), zl);
     chunk("IEND", nullptr, 0);
+  }
+  if (fclose(fp) != 0 && rc == GI_OK) rc = GI_ERR_IO;
+  return rc;
+}
+
+// Float frames (radiance): no reference counterpart, the reference writes 8-bit images only.
+//   .pfm  "PF\nW H\n-1.0\n" + the rows bottom to top as little-endian float32: the array as it is
+//   .hdr  Radiance picture, flat RGBE scanlines from the top row. A pixel is Ward's setcolr
+//         (color.c): e = exponent of frexp(largest channel), byte = (int)(c * 2^(8 - e)),
+//         fourth byte e + 128. Ward scales by frexp(v) * 256 / v, which is 2^(8 - e) up to the
+//         rounding of the division; the power of two is taken directly, so a channel on a byte
+//         boundary truncates to that byte.
+int gi_write_image_float(const char *path, int w, int h, const float *rgbf) {
+  if (!path || !rgbf || w <= 0 || h <= 0) return GI_ERR_ARG;
+  const char *ext = strrchr(path, '.');
+  if (!ext) return GI_ERR_ARG;
+  const bool pfm = strcmp(ext, ".pfm") == 0, hdr = strcmp(ext, ".hdr") == 0;
+  if (!pfm && !hdr) return GI_ERR_ARG;
+  FILE *fp = fopen(path, "wb");
+  if (!fp) return GI_ERR_IO;
+  int rc = GI_OK;
+  const size_t nrow = (size_t)w * 3;
+  if (pfm) {
+    fprintf(fp, "PF\n%d %d\n-1.0\n", w, h);
+    if (fwrite(rgbf, 4, nrow * h, fp) != nrow * h) rc = GI_ERR_IO;
+  } else {
+    fprintf(fp, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n", h, w);
+    std::vector<uint8_t> line((size_t)w * 4);
+    for (int j = h - 1; j >= 0 && rc == GI_OK; j--) {
+      const float *p = rgbf + (size_t)j * nrow;
+      for (int i = 0; i < w; i++) {
+        const double c[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+        double v = c[0] > c[1] ? c[0] : c[1];
+        if (c[2] > v) v = c[2];
+        uint8_t *o = &line[(size_t)i * 4];
+        if (!(v >= 1e-32)) {  // also NaN
+          o[0] = o[1] = o[2] = o[3] = 0;
+          continue;
+        }
+        int e = 0;
+        frexp(v, &e);
+        if (e > 127) {  // 2^127 and above (infinity too): the largest pixel the format holds
+          o[0] = o[1] = o[2] = o[3] = 255;
+          continue;
+        }
+        const double s = ldexp(1.0, 8 - e);
+        for (int k = 0; k < 3; k++) o[k] = c[k] > 0.0 ? (uint8_t)(int)(c[k] * s) : 0;
+        o[3] = (uint8_t)(e + 128);
+      }
+      if (fwrite(line.data(), 1, line.size(), fp) != line.size()) rc = GI_ERR_IO;
+    }
   }
   if (fclose(fp) != 0 && rc == GI_OK) rc = GI_ERR_IO;
   return rc;

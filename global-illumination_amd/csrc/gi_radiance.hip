@@ -1,0 +1,143 @@
+// gi_radiance.hip -- unclamped radiance frames, the accumulator over passes and the tone map
+// (gfx950). No reference counterpart (the reference keeps the clamped 8-bit frame only).
+// DESIGN.md "Radiance frames, accumulation and tone map" holds the definitions;
+// tests/radiance_ref.py restates them in numpy and every kernel matches it bit for bit: each
+// operation here is one of + - * / sqrt in fp64, left to right, compiled with -ffp-contract=off.
+//
+//   reduce_radiance_kernel   one thread per output pixel of a batch: the samples reduce_kernel
+//                            clamps, unclamped; their box-filtered mean m and M2 = sum (s - m)^2
+//   accum_merge_kernel       one thread per pixel: a finished pass folded into the accumulator
+//   radiance_resolve_kernel  {m, M2} of n samples -> float mean and variance of the mean
+//   accum_noise_kernel       relative standard error of luminance, block tree sum
+//   tonemap_kernel           exposure, extended Reinhard curve, clamp
+#include <hip/hip_runtime.h>
+#include "gi_radiance.h"
+
+namespace gi {
+
+static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+// sample j of batch pixel pix: reduce_kernel's value before its clamp
+__device__ __forceinline__ void radiance_sample(const RadianceArgs &a, int pix, int j, double &s0,
+                                                double &s1, double &s2) {
+  s0 = 0; s1 = 0; s2 = 0;
+  for (int k = 0; k < a.dof_test; k++) {
+    const int64_t b = ((int64_t)pix * a.S + j) * a.dof_test + k;
+    s0 += a.prim_rgb[3 * b];
+    s1 += a.prim_rgb[3 * b + 1];
+    s2 += a.prim_rgb[3 * b + 2];
+  }
+  s0 /= a.dof_test; s1 /= a.dof_test; s2 /= a.dof_test;
+}
+
+// The second loop reads the pixel's primaries again (S * dof_test * 24 B, just read: L2) rather
+// than keeping S samples in registers, so S is not bounded.
+__global__ __launch_bounds__(64) void reduce_radiance_kernel(RadianceArgs a) {
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= a.npix) return;
+  const int2 pc = a.pixels[pix];
+  const int64_t o = (int64_t)pc.y * a.out_w + pc.x;
+  double *smp = a.samples ? a.samples + o * a.S * 3 : nullptr;
+  double acc0 = 0, acc1 = 0, acc2 = 0;
+  for (int j = 0; j < a.S; j++) {
+    double s0, s1, s2;
+    radiance_sample(a, pix, j, s0, s1, s2);
+    if (smp) {
+      smp[3 * j] = s0;
+      smp[3 * j + 1] = s1;
+      smp[3 * j + 2] = s2;
+    }
+    acc0 += s0; acc1 += s1; acc2 += s2;
+  }
+  const double m0 = a.bw * acc0, m1 = a.bw * acc1, m2 = a.bw * acc2;
+  double q0 = 0, q1 = 0, q2 = 0;
+  for (int j = 0; j < a.S; j++) {
+    double s0, s1, s2;
+    radiance_sample(a, pix, j, s0, s1, s2);
+    q0 += (s0 - m0) * (s0 - m0);
+    q1 += (s1 - m1) * (s1 - m1);
+    q2 += (s2 - m2) * (s2 - m2);
+  }
+  double *f = a.frame + o * 6;
+  f[0] = m0; f[1] = m1; f[2] = m2;
+  f[3] = q0; f[4] = q1; f[5] = q2;
+}
+
+// Chan et al.'s pairwise update of (count, mean, M2); an empty accumulator takes the pass as is
+__global__ __launch_bounds__(256) void accum_merge_kernel(AccumArgs a) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.npix) return;
+  const double *f = a.pass + p * 6;
+  double *g = a.acc + p * 6;
+  if (a.N == 0) {
+    for (int c = 0; c < 6; c++) g[c] = f[c];
+    return;
+  }
+  const double S = (double)a.S, N1 = (double)(a.N + a.S), NS = (double)a.N * S;
+  for (int c = 0; c < 3; c++) {
+    const double d = f[c] - g[c];
+    g[c] = g[c] + (d * S) / N1;
+    g[3 + c] = (g[3 + c] + f[3 + c]) + ((d * d) * NS) / N1;
+  }
+}
+
+__global__ __launch_bounds__(256) void radiance_resolve_kernel(ResolveArgs a) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.npix) return;
+  const double *f = a.frame + p * 6;
+  const double n = (double)a.n, n1 = (double)(a.n - 1);
+  for (int c = 0; c < 3; c++) {
+    if (a.mean) a.mean[3 * p + c] = (float)f[c];
+    if (a.variance) a.variance[3 * p + c] = a.n < 2 ? 0.0f : (float)(f[3 + c] / n1 / n);
+  }
+}
+
+__global__ __launch_bounds__(NOISE_BLOCK) void accum_noise_kernel(NoiseArgs a) {
+  __shared__ double x[NOISE_BLOCK];
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * NOISE_BLOCK + t;
+  double e = 0.0;
+  if (p < a.npix && a.n >= 2) {
+    const double *f = a.acc + p * 6;
+    const double n = (double)a.n, n1 = (double)(a.n - 1);
+    const double Y = 0.2126 * f[0] + 0.7152 * f[1] + 0.0722 * f[2];
+    const double v = (0.2126 * 0.2126) * (f[3] / n1 / n) + (0.7152 * 0.7152) * (f[4] / n1 / n) +
+                     (0.0722 * 0.0722) * (f[5] / n1 / n);
+    e = sqrt(v) / (Y + 0.01);
+  }
+  x[t] = e;
+  __syncthreads();
+  for (int h = NOISE_BLOCK / 2; h >= 1; h >>= 1) {
+    if (t < h) x[t] += x[t + h];
+    __syncthreads();
+  }
+  if (t == 0) a.partial[blockIdx.x] = x[0];
+}
+
+__global__ __launch_bounds__(256) void tonemap_kernel(TonemapArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.nval) return;
+  const double x = a.exposure * (double)a.in[i];
+  double y = x;
+  if (a.white > 0.0) y = (x * (1.0 + x / (a.white * a.white))) / (1.0 + x);
+  y = y < 0.0 ? 0.0 : (y > 1.0 ? 1.0 : y);
+  a.out[i] = (float)y;
+}
+
+void launch_reduce_radiance(const RadianceArgs &a, hipStream_t st) {
+  if (a.npix > 0) reduce_radiance_kernel<<<nblk(a.npix, 64), 64, 0, st>>>(a);
+}
+void launch_accum_merge(const AccumArgs &a, hipStream_t st) {
+  if (a.npix > 0) accum_merge_kernel<<<nblk(a.npix, 256), 256, 0, st>>>(a);
+}
+void launch_radiance_resolve(const ResolveArgs &a, hipStream_t st) {
+  if (a.npix > 0) radiance_resolve_kernel<<<nblk(a.npix, 256), 256, 0, st>>>(a);
+}
+void launch_accum_noise(const NoiseArgs &a, hipStream_t st) {
+  if (a.npix > 0) accum_noise_kernel<<<nblk(a.npix, NOISE_BLOCK), NOISE_BLOCK, 0, st>>>(a);
+}
+void launch_tonemap(const TonemapArgs &a, hipStream_t st) {
+  if (a.nval > 0) tonemap_kernel<<<nblk(a.nval, 256), 256, 0, st>>>(a);
+}
+
+}  // namespace gi

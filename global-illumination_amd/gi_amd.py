@@ -10,6 +10,10 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
   materials / camera_features / ray_features / denoise: per-pixel feature planes and the
                    edge-avoiding denoise pass (no reference counterpart; gi.h "feature planes
                    and denoise pass")
+  render_radiance / render_rays_radiance / accum_* / tonemap / write_image_float: unclamped
+                   radiance frames with their variance, accumulation over passes and the tone
+                   map (no reference counterpart; gi.h "radiance frames, accumulation over
+                   passes, tone map")
   EstimateRadiance utils/photon_utils.cpp:72-162      (batched test seam)
   FindClosestQuick R3Shapes/R3Kdtree.cpp:688-848      (batched test seam)
   Intersects       R3Graphics/R3Scene.cpp:471-479     (batched test seam)
@@ -38,9 +42,11 @@ EXPORTED = [
     "gi_render_tiles_packed", "gi_compose_tiles", "gi_quantize",
     "gi_get_materials", "gi_camera_features", "gi_ray_features", "gi_denoise_params_default",
     "gi_denoise",
+    "gi_render_radiance", "gi_render_rays_radiance", "gi_accum_reset", "gi_accum_add_image",
+    "gi_accum_add_rays", "gi_accum_get", "gi_tonemap", "gi_radiance_bench",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
-    "gi_write_image",
+    "gi_write_image", "gi_write_image_float",
 ]
 
 
@@ -194,6 +200,22 @@ def lib():
         L.gi_denoise_params_default.restype = None
         L.gi_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  P(DenoiseParams), C.c_void_p, C.c_void_p, P(C.c_double)]
+        L.gi_render_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, P(RenderStats)]
+        L.gi_render_rays_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              P(RenderStats)]
+        L.gi_accum_reset.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.gi_accum_add_image.argtypes = [C.c_void_p, C.c_int, P(RenderStats)]
+        L.gi_accum_add_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        P(RenderStats)]
+        L.gi_accum_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64),
+                                   P(C.c_double)]
+        L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                 C.c_double, C.c_void_p, C.c_void_p]
+        L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        P(C.c_double), P(C.c_double), P(C.c_double)]
+        L.gi_write_image_float.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p]
         L.gi_estimate_radiance_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         L.gi_knn_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
@@ -372,15 +394,20 @@ class Renderer:
                                          ids.ctypes.data, n.value, C.byref(n)))
         return rays, ids
 
-    def render_rays(self, width, height, spp, rays, ids=None, want_float=False):
-        """Render caller-made primary rays, spp per output pixel (gi_render_rays); returns like
-        RenderImage. ids: RNG stream id per ray (default: the ray's index)."""
+    def _ray_batch(self, width, height, spp, rays, ids):
+        """Contiguous rays and ids of a width x height x spp batch, lengths checked."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
         if ids is not None:
             ids = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
         need = width * height * spp
         if spp >= 1 and (len(rays) != need or (ids is not None and len(ids) != need)):
             raise ValueError(f"{need} rays expected (width * height * spp), got {len(rays)}")
+        return rays, ids
+
+    def render_rays(self, width, height, spp, rays, ids=None, want_float=False):
+        """Render caller-made primary rays, spp per output pixel (gi_render_rays); returns like
+        RenderImage. ids: RNG stream id per ray (default: the ray's index)."""
+        rays, ids = self._ray_batch(width, height, spp, rays, ids)
         rgb = np.zeros((height, width, 3), dtype=np.uint8)
         rgbf = np.zeros((height, width, 3), dtype=np.float32) if want_float else None
         st = RenderStats()
@@ -439,6 +466,101 @@ class Renderer:
         self._check(lib().gi_denoise(self._ctx, w, h, rgbf.ctypes.data, feat.ctypes.data,
                                      C.byref(p), out.ctypes.data, rgb.ctypes.data, C.byref(ms)))
         return (rgb, out, ms.value) if want_float else (rgb, ms.value)
+
+    def render_radiance(self, aa, width, height, want_samples=False):
+        """Unclamped frame of RenderImage(aa, width, height) (gi_render_radiance): (mean
+        [H, W, 3] float32, variance of the mean [H, W, 3] float32, stats), or with want_samples
+        (mean, variance, samples [H, W, 4^aa, 3] float64, stats)."""
+        S = 4 ** aa if 0 <= aa <= 15 else 1
+        mean = np.zeros((height, width, 3), dtype=np.float32)
+        var = np.zeros((height, width, 3), dtype=np.float32)
+        smp = np.zeros((height, width, S, 3), dtype=np.float64) if want_samples else None
+        st = RenderStats()
+        self._check(lib().gi_render_radiance(self._ctx, aa, width, height, mean.ctypes.data,
+                                             var.ctypes.data,
+                                             smp.ctypes.data if want_samples else None,
+                                             C.byref(st)))
+        stats = _stats_dict(st)
+        return (mean, var, smp, stats) if want_samples else (mean, var, stats)
+
+    def render_rays_radiance(self, width, height, spp, rays, ids=None, want_samples=False):
+        """Unclamped frame of a caller-made ray batch, spp rays per pixel as in render_rays
+        (gi_render_rays_radiance); returns like render_radiance, samples [H, W, spp, 3]."""
+        rays, ids = self._ray_batch(width, height, spp, rays, ids)
+        mean = np.zeros((height, width, 3), dtype=np.float32)
+        var = np.zeros((height, width, 3), dtype=np.float32)
+        smp = (np.zeros((height, width, max(spp, 1), 3), dtype=np.float64) if want_samples
+               else None)
+        st = RenderStats()
+        self._check(lib().gi_render_rays_radiance(
+            self._ctx, width, height, spp, rays.ctypes.data,
+            None if ids is None else ids.ctypes.data, mean.ctypes.data, var.ctypes.data,
+            smp.ctypes.data if want_samples else None, C.byref(st)))
+        stats = _stats_dict(st)
+        return (mean, var, smp, stats) if want_samples else (mean, var, stats)
+
+    def accum_reset(self, width, height):
+        """Size and empty the context's accumulator over passes (gi_accum_reset)."""
+        self._check(lib().gi_accum_reset(self._ctx, width, height))
+        self._accum_size = (width, height)
+
+    def accum_add_image(self, aa):
+        """Render one camera pass under the current parameters and fold it into the accumulator
+        (gi_accum_add_image); change params.seed with set_params between passes: the photon maps
+        stay. Returns the pass's stats."""
+        st = RenderStats()
+        self._check(lib().gi_accum_add_image(self._ctx, aa, C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_add_rays(self, spp, rays, ids=None):
+        """Render one ray pass of the accumulator's size and fold it in (gi_accum_add_rays); give
+        other ids for every pass."""
+        w, h = getattr(self, "_accum_size", (0, 0))
+        if w:
+            rays, ids = self._ray_batch(w, h, spp, rays, ids)
+        else:  # no reset yet: the library reports it
+            rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+            ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        st = RenderStats()
+        self._check(lib().gi_accum_add_rays(self._ctx, spp, rays.ctypes.data,
+                                            None if ids is None else ids.ctypes.data,
+                                            C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_get(self):
+        """(mean [H, W, 3] float32, variance of the mean [H, W, 3] float32, samples per pixel N,
+        noise: the frame's mean relative standard error of luminance) of the accumulator
+        (gi_accum_get)."""
+        w, h = getattr(self, "_accum_size", (0, 0))
+        mean = np.zeros((h, w, 3), dtype=np.float32)
+        var = np.zeros((h, w, 3), dtype=np.float32)
+        n, noise = C.c_int64(0), C.c_double(0.0)
+        self._check(lib().gi_accum_get(self._ctx, mean.ctypes.data if w else None,
+                                       var.ctypes.data if w else None, C.byref(n),
+                                       C.byref(noise)))
+        return mean, var, n.value, noise.value
+
+    def tonemap(self, radiance, exposure=1.0, white=0.0, want_float=False):
+        """Exposure, extended Reinhard curve (white > 0; 0: linear) and clamp of a radiance frame
+        [H, W, 3] (gi_tonemap). Returns rgb8, or (rgb8, rgbf) with want_float."""
+        radiance = np.ascontiguousarray(radiance, dtype=np.float32)
+        if radiance.ndim != 3 or radiance.shape[2] != 3:
+            raise ValueError(f"[H, W, 3] frame expected, got {radiance.shape}")
+        h, w, _ = radiance.shape
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        self._check(lib().gi_tonemap(self._ctx, w, h, radiance.ctypes.data, exposure, white,
+                                     out.ctypes.data, rgb.ctypes.data))
+        return (rgb, out) if want_float else rgb
+
+    def radiance_bench(self, aa, width, height, warmup=5, reps=50):
+        """Median HIP-event ms of the radiance reduction, the accumulator merge and the noise
+        reduction on a synthetic frame (diagnostics; gi_radiance_bench)."""
+        t = [C.c_double(0.0) for _ in range(3)]
+        self._check(lib().gi_radiance_bench(self._ctx, aa, width, height, warmup, reps,
+                                            C.byref(t[0]), C.byref(t[1]), C.byref(t[2])))
+        return {"reduce_radiance_ms": t[0].value, "accum_merge_ms": t[1].value,
+                "accum_noise_ms": t[2].value}
 
     def render_tiles(self, aa, width, height, tile, shard, nshards, rgbf=None):
         if rgbf is None:
@@ -544,3 +666,13 @@ def write_image(path, rgb):
     rc = lib().gi_write_image(path.encode(), w, h, rgb.ctypes.data)
     if rc != GI_OK:
         raise GiError(f"gi_write_image({path}) rc={rc}")
+
+
+def write_image_float(path, rgbf):
+    """rgbf: float32 [H, W, 3] with row 0 = bottom, written as .pfm or .hdr
+    (gi_write_image_float)."""
+    rgbf = np.ascontiguousarray(rgbf, dtype=np.float32)
+    h, w, _ = rgbf.shape
+    rc = lib().gi_write_image_float(path.encode(), w, h, rgbf.ctypes.data)
+    if rc != GI_OK:
+        raise GiError(f"gi_write_image_float({path}) rc={rc}")

@@ -8,6 +8,11 @@
 // scene file's (gi_set_camera; the numbers of the .scn `camera` command).
 // Extension: -denoise L writes the frame filtered by L (1..8) levels of the edge-avoiding
 // a-trous pass over its feature planes (gi_camera_features + gi_denoise, default parameters).
+// Extension: -passes N (1..4096), -noise T, -exposure E, -white W, -radiance FILE. With any of
+// them the maps are built once, pass i is rendered under seed + i and folded into the context's
+// accumulator (gi_accum_*), after each pass -noise stops at noise <= T (default passes: 1, or
+// 4096 under -noise), the written image is gi_tonemap of the unclamped mean (E default 1, W
+// default 0: linear) and FILE (.pfm / .hdr) receives that mean. One device only.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +81,76 @@ static bool TakeDenoise(int &argc, char **argv, int &levels) {
   return true;
 }
 
+// Takes `flag value` out of argv in the same way: *value = the last one's text (null when the
+// flag is absent); false when the flag is last in argv.
+static bool TakeValue(int &argc, char **argv, const char *flag, const char **value) {
+  for (int a = 1; a < argc;) {
+    if (strcmp(argv[a], flag)) { a++; continue; }
+    if (a + 1 >= argc) return false;
+    *value = argv[a + 1];
+    for (int k = a + 2; k < argc; k++) argv[k - 2] = argv[k];
+    argc -= 2;
+  }
+  return true;
+}
+static bool ParseNumber(const char *text, double *v) {
+  char *end = nullptr;
+  *v = strtod(text, &end);
+  return end != text && !*end && *v == *v && *v - *v == 0.0;  // a finite number, nothing after it
+}
+
+// -passes / -noise / -exposure / -white / -radiance
+struct RadianceFlags {
+  bool any = false, have_noise = false;
+  int passes = 0;  // 0: not given
+  double noise = 0.0, exposure = 1.0, white = 0.0;
+  const char *file = nullptr;
+};
+// null, or the flag that is malformed
+static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
+  const char *t = nullptr;
+  double v = 0.0;
+  if (!TakeValue(argc, argv, "-passes", &t)) return "-passes";
+  if (t) {
+    char *end = nullptr;
+    const long n = strtol(t, &end, 10);
+    if (end == t || *end || n < 1 || n > 4096) return "-passes";
+    r.passes = (int)n;
+    r.any = true;
+  }
+  t = nullptr;
+  if (!TakeValue(argc, argv, "-noise", &t)) return "-noise";
+  if (t) {
+    if (!ParseNumber(t, &v) || v < 0.0) return "-noise";
+    r.noise = v;
+    r.have_noise = r.any = true;
+  }
+  t = nullptr;
+  if (!TakeValue(argc, argv, "-exposure", &t)) return "-exposure";
+  if (t) {
+    if (!ParseNumber(t, &v) || !(v > 0.0)) return "-exposure";
+    r.exposure = v;
+    r.any = true;
+  }
+  t = nullptr;
+  if (!TakeValue(argc, argv, "-white", &t)) return "-white";
+  if (t) {
+    if (!ParseNumber(t, &v) || v < 0.0) return "-white";
+    r.white = v;
+    r.any = true;
+  }
+  t = nullptr;
+  if (!TakeValue(argc, argv, "-radiance", &t)) return "-radiance";
+  if (t) {
+    const char *ext = strrchr(t, '.');
+    if (!ext || (strcmp(ext, ".pfm") && strcmp(ext, ".hdr"))) return "-radiance";
+    r.file = t;
+    r.any = true;
+  }
+  if (r.passes == 0) r.passes = r.have_noise ? 4096 : 1;
+  return nullptr;
+}
+
 int main(int argc, char **argv) {
   gi_camera cam;
   bool have_cam = false;
@@ -86,6 +161,11 @@ int main(int argc, char **argv) {
   int denoise_levels = 0;  // 0: no denoise pass
   if (!TakeDenoise(argc, argv, denoise_levels)) {
     fprintf(stderr, "Invalid program argument: -denoise");
+    return 1;
+  }
+  RadianceFlags rad;
+  if (const char *bad = TakeRadiance(argc, argv, rad)) {
+    fprintf(stderr, "Invalid program argument: %s", bad);
     return 1;
   }
   gi_params P;
@@ -119,6 +199,11 @@ int main(int argc, char **argv) {
       if (*q == ',') q++;
     }
     if (ds.count == 0) ds.count = 1;
+  }
+  if (rad.any && ds.count > 1) {
+    fprintf(stderr, "-passes, -noise, -exposure, -white and -radiance render on one device: not with -gpus %d\n",
+            ds.count);
+    return -1;
   }
   gi_ctx *ctx = nullptr;
   if (gi_create_devices(&ctx, &ds) != GI_OK) {
@@ -173,8 +258,46 @@ int main(int argc, char **argv) {
   std::vector<uint8_t> rgb((size_t)w * h * 3);
   gi_render_stats rs;
   if (P.verbose) printf("Rendering image ...\n");
-  std::vector<float> rgbf(denoise_levels ? (size_t)w * h * 3 : 0);
-  if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
+  std::vector<float> rgbf(denoise_levels || rad.any ? (size_t)w * h * 3 : 0);
+  std::vector<float> mean(rad.any ? (size_t)w * h * 3 : 0);
+  int passes_done = 0;
+  long long acc_n = 0;
+  double acc_noise = 0.0;
+  if (rad.any) {
+    // passes under seed, seed + 1, ... from the same maps, folded into the accumulator; the
+    // written image is the tone-mapped unclamped mean
+    memset(&rs, 0, sizeof rs);
+    bool ok = gi_accum_reset(ctx, w, h) == GI_OK;
+    for (int i = 0; ok && i < rad.passes; i++) {
+      gi_params Pi = P;
+      Pi.seed = P.seed + (uint64_t)i;
+      gi_render_stats ps;
+      prog.last[0] = -1;
+      ok = gi_set_params(ctx, &Pi) == GI_OK && gi_accum_add_image(ctx, aa, &ps) == GI_OK;
+      if (!ok) break;
+      passes_done++;
+      rs.render_s += ps.render_s;
+      rs.screen_rays += ps.screen_rays; rs.shadow_rays += ps.shadow_rays;
+      rs.monte_carlo_rays += ps.monte_carlo_rays; rs.transmissive_samples += ps.transmissive_samples;
+      rs.specular_samples += ps.specular_samples; rs.indirect_samples += ps.indirect_samples;
+      rs.caustic_samples += ps.caustic_samples;
+      if (rad.have_noise) {  // defined from two samples per pixel on
+        int64_t n = 0;
+        ok = gi_accum_get(ctx, nullptr, nullptr, &n, &acc_noise) == GI_OK;
+        if (ok && n >= 2 && acc_noise <= rad.noise) break;
+      }
+    }
+    int64_t n = 0;
+    ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK &&
+         gi_tonemap(ctx, w, h, mean.data(), rad.exposure, rad.white, rgbf.data(), rgb.data()) == GI_OK;
+    acc_n = n;
+    gi_set_params(ctx, &P);
+    if (!ok) {
+      fprintf(stderr, "%s\n", gi_last_error(ctx));
+      gi_destroy(ctx);
+      return -1;
+    }
+  } else if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
     fprintf(stderr, "%s\n", gi_last_error(ctx));
     gi_destroy(ctx);
     return -1;
@@ -207,6 +330,9 @@ int main(int argc, char **argv) {
     if (P.indirect_illum) { printf("  # Indirect Samples = %llu\n", (unsigned long long)rs.indirect_samples); total += rs.indirect_samples; }
     if (P.caustic_illum) { printf("  # Caustic Samples = %llu\n", (unsigned long long)rs.caustic_samples); total += rs.caustic_samples; }
     printf("Total Rays: %llu\n", total);
+    if (rad.any)
+      printf("Accumulated image: %d passes, N = %lld samples per pixel, noise = %.6g\n", passes_done,
+             acc_n, acc_noise);
     if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);
     fflush(stdout);
   }
@@ -216,6 +342,10 @@ int main(int argc, char **argv) {
     const char *ext = strrchr(out, '.');
     if (ext && !strncmp(ext, ".tif", 4)) fprintf(stderr, "TIFF not supported\n");  // R2Image.cpp:1300
     else fprintf(stderr, "Unable to write image %s\n", out);
+    return -1;
+  }
+  if (rad.file && gi_write_image_float(rad.file, w, h, mean.data()) != GI_OK) {
+    fprintf(stderr, "Unable to write image %s\n", rad.file);
     return -1;
   }
   if (P.verbose) {

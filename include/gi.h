@@ -335,6 +335,57 @@ int gi_denoise(gi_ctx *ctx, int width, int height, const float *rgbf,
                const gi_pixel_features *feat, const gi_denoise_params *p,
                float *out_rgbf, uint8_t *out_rgb8, double *kernel_ms);
 
+/* ---- radiance frames, accumulation over passes, tone map -------------------------------- */
+/* gi_render_image / gi_render_rays clamp every sample to [0, 1] before the box filter (the
+ * reference's 8-bit output path) and return only the result. These calls return what the clamp
+ * sees (DESIGN.md "Radiance frames, accumulation and tone map"). No reference counterpart.
+ * All of them are for contexts over one device: on a device set (gi_create_devices) the renders
+ * and the accumulator calls return GI_ERR_UNSUPPORTED (the tile gather packs 16 B per pixel).
+ *
+ * A pixel has S samples: S = 4^aa sub-cells of a camera frame (each the mean of its dof_test lens
+ * samples), S = spp rays of a ray batch. Sample s_j is the fp64 value gi_render_image has before
+ * its clamp. With bw = 1.0 / af / af (af = 2^aa) or 1.0 / spp, sums in sample order in fp64:
+ *   m = bw * sum_j s_j,  M2 = sum_j (s_j - m)^2,
+ *   mean = (float)m,  variance = (float)(M2 / (S - 1) / S), the variance of the mean (0 for S = 1).
+ * mean, variance: W*H*3 floats, rows from the bottom; samples: W*H*S*3 doubles, pixel-major,
+ * then sample, then r, g, b. Any of the three may be NULL, not all. Pipeline, batches, counters
+ * and argument checks are gi_render_image's / gi_render_rays' (aa <= 15 here). */
+int gi_render_radiance(gi_ctx *ctx, int aa, int width, int height, float *mean, float *variance,
+                       double *samples, gi_render_stats *stats);
+int gi_render_rays_radiance(gi_ctx *ctx, int width, int height, int spp, const gi_ray *rays,
+                            const uint64_t *ids /* may be NULL */, float *mean, float *variance,
+                            double *samples, gi_render_stats *stats);
+/* Accumulator, on the device, one per context: per pixel and channel a running fp64 mean mu and
+ * sum of squared deviations A, and one sample count N for the frame. gi_accum_reset sizes and
+ * empties it (N = 0). gi_accum_add_image / gi_accum_add_rays render one pass of the reset's
+ * width x height under the context's current parameters and fold its (S, m, M2) in, once, after
+ * the render has completed; the first pass is taken as is, later ones by
+ *   d = m - mu,  N' = N + S,  mu' = mu + (d * S) / N',  A' = (A + M2) + ((d * d) * (N * S)) / N'.
+ * The caller decorrelates the passes: for camera passes change `seed` with gi_set_params between
+ * them (gi_set_params keeps the photon maps, their kd trees and the -cache irradiance: a second
+ * render under another seed is an independent estimate from the same maps); for ray passes give
+ * other ids. gi_accum_get (every output optional): mean = (float)mu, variance =
+ * (float)(A / (N - 1) / N) (0 when N < 2), *nsamples = N, *noise = the mean over the pixels of
+ * sqrt(v) / (Y + 0.01) with Y = 0.2126 mu_r + 0.7152 mu_g + 0.0722 mu_b and v = 0.2126^2 v_r +
+ * 0.7152^2 v_g + 0.0722^2 v_b (v_c the unrounded A / (N - 1) / N): the relative standard error
+ * of luminance, summed in a fixed order (blocks of 256 pixels by a tree, then block by block),
+ * so the same accumulator always reports the same bits; 0 when N < 2. GI_ERR_STATE before a
+ * reset; a pass always has the reset's size (a ray pass takes width * height * spp rays). */
+int gi_accum_reset(gi_ctx *ctx, int width, int height);
+int gi_accum_add_image(gi_ctx *ctx, int aa, gi_render_stats *stats);
+int gi_accum_add_rays(gi_ctx *ctx, int spp, const gi_ray *rays, const uint64_t *ids,
+                      gi_render_stats *stats);
+int gi_accum_get(gi_ctx *ctx, float *mean, float *variance, int64_t *nsamples, double *noise);
+/* Tone map of a radiance frame (W*H*3 floats), per channel in fp64: x = exposure * c;
+ * y = x * (1 + x / (white * white)) / (1 + x) when white > 0 (extended Reinhard: `white` maps to
+ * 1), y = x when white == 0; clamped to [0, 1], rounded to float32. Linear output, as the
+ * reference writes (no gamma). out_rgbf and out_rgb8 = gi_quantize of out_rgbf: either may be
+ * NULL, not both. GI_ERR_ARG for an exposure that is not finite and positive, a white that is
+ * negative or not finite, null buffers or a bad size. Needs only a context; runs on its first
+ * device (also on a device set). */
+int gi_tonemap(gi_ctx *ctx, int width, int height, const float *radiance, double exposure,
+               double white, float *out_rgbf, uint8_t *out_rgb8);
+
 /* ---- test seams ----------------------------------------------------------------------- */
 /* n <= 2^26 queries per call (GI_ERR_ARG above). */
 int gi_estimate_radiance_batch(gi_ctx *ctx, int map, int64_t n, const gi_radiance_query *q,
@@ -349,6 +400,12 @@ int gi_knn_batch(gi_ctx *ctx, int map, int64_t n, const double *points, int k, d
 int gi_knn_bench(gi_ctx *ctx, int map, int64_t n, const double *points, const double *normals,
                  const int32_t *materials, int mode, int kernel, int iters, double *ms_per_launch,
                  double *found_per_query, double *visited_per_query);
+/* Diagnostics: time the radiance reduction, the accumulator merge and the noise reduction on a
+ * synthetic width x height frame of 4^aa samples per pixel (dof_test 1), each launch between two
+ * HIP events: the median of `reps` launches after `warmup` ones, in ms (outputs optional). Needs
+ * only a context; leaves its accumulator alone. No reference counterpart (measurement only). */
+int gi_radiance_bench(gi_ctx *ctx, int aa, int width, int height, int warmup, int reps,
+                      double *reduce_ms, double *merge_ms, double *noise_ms);
 int gi_intersect_batch(gi_ctx *ctx, int64_t n, const double *org, const double *dir,
                        int32_t *hit, double *t, double *point, double *normal, int32_t *material);
 /* Test seam: the device's fp64 math on host inputs, fn = 0 acos(x), 1 sin(x), 2 cos(x),
@@ -366,6 +423,12 @@ int gi_release_scratch(gi_ctx *ctx);
 
 /* ---- output --------------------------------------------------------------------------- */
 int gi_write_image(const char *path, int width, int height, const uint8_t *rgb8);
+/* Float image (W*H*3, rows from the bottom) by extension: .pfm = "PF", little-endian (scale
+ * -1.0), rows bottom to top, so the pixel bytes are the array; .hdr = Radiance "#?RADIANCE",
+ * FORMAT=32-bit_rle_rgbe, "-Y H +X W", flat (not run-length encoded) scanlines from the top row,
+ * Ward's RGBE (frexp of the largest channel, mantissa bytes truncated, exponent + 128; four zero
+ * bytes when it is below 1e-32). Any other extension: GI_ERR_ARG. No reference counterpart. */
+int gi_write_image_float(const char *path, int width, int height, const float *rgbf);
 
 #ifdef __cplusplus
 }
