@@ -102,6 +102,15 @@ struct DBuf {
   }
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+// A function's own scratch: freed when it goes out of scope, on every return path. (DBuf itself
+// has no destructor: gi_destroy frees the context's members in its own order, device by device.)
+// Declared after the function's DeviceScope, so that it is freed on the right device.
+struct TmpBuf : DBuf {
+  TmpBuf() = default;
+  TmpBuf(const TmpBuf &) = delete;
+  TmpBuf &operator=(const TmpBuf &) = delete;
+  ~TmpBuf() { release(); }
+};
 
 // RNRgb_to_RGBE / RGBE_to_RNRgb (graphics_utils.cpp:50-77), host side
 void rgbe_enc(const double c[3], uint8_t *out) {
@@ -290,6 +299,13 @@ Rccl g_rccl;
 // =======================================================================================
 // Execution state of one photon map's k-NN launches (stream, timing events, scratch). One per
 // map, so the two maps' estimates can run concurrently on two streams during a render.
+// The queries a chunk k-NN pass hands on (gi_knn_chunk.hip to_fallback): FB_QS stripes of query
+// ids with their fill counters, and the same ids compacted (dense[n] = their number, n the
+// pass's queries).
+struct FbList {
+  DBuf list, count, dense;
+};
+
 struct MapExec {
   hipStream_t st = nullptr;        // the ctx stream, or the side stream while maps overlap
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;  // chunk pass | second
@@ -297,8 +313,8 @@ struct MapExec {
   SortScratch sorter;              // Morton order of the query list
   DBuf list_idx, list_d2, list_n;  // K-best lists of the query-per-wave k-NN path
   DBuf gheap_d2, gheap_idx;        // global-memory heaps (K > 64 per-lane kernel)
-  DBuf fb_list, fb_count, fb_dense;     // chunk k-NN fallback queries (striped, compacted)
-  DBuf fb_list2, fb_count2, fb_dense2;  // large-K chunk k-NN: second pass's fallback queries
+  FbList fb[2];                    // chunk k-NN: the first pass writes fb[0], each further pass
+                                   // the one its input is not in (run_chunk_knn)
   DBuf dk_q;                       // photon positions as queries (ensure_dk)
   uint64_t fb_total = 0;
 };
@@ -345,7 +361,7 @@ struct gi_ctx {
   uint64_t fb_q[2] = {0, 0};      // last reset)
   double p2_ms[2] = {0, 0};       // second chunk pass's time and queries per map
   uint64_t p2_q[2] = {0, 0};
-  int last_kind[2] = {-1, -1};
+  int last_kind[2] = {-1, -1};     // k-NN kind run_knn chose last, per map (gi_render_stats)
   bool knn_log = false;            // GI_LOG & 4: one stderr line per chunk k-NN launch
   int knn_dbg = 0;                 // GI_KNN_DBG: k-NN kernel diagnostics (KnnArgs::dbg)
   int render_dbg = 0;              // GI_DBG: render-kernel diagnostics (RenderArgs::dbg)
@@ -353,7 +369,7 @@ struct gi_ctx {
   int elem_pretest = -1;           // GI_ELEM_PRETEST: -1 auto (make_view), 0 off, 1 on
   gi_progress_fn progress = nullptr;  // gi_set_progress
   void *progress_user = nullptr;
-  int64_t progress_done = 0, progress_total = 0;  // output pixels of the current RenderImage     // k-NN kind run_knn chose last, per map (gi_render_stats)
+  int64_t progress_done = 0, progress_total = 0;  // output pixels of the current RenderImage
   int sel_slack = 64;
   int knn_qpl = 1;
   DBuf ind_cont, ind_ncont;       // indirect paths that continue past their first bounce
@@ -403,7 +419,7 @@ struct gi_ctx {
   bool surf_key_c = true;           // caustic list: 64-bit surface keys (surf64_valid_kernel)
   bool fb_wave = true;              // chunk kernel's last fallback: the query-per-wave kernel (r06; the per-lane one: GI_FB_WAVE=0)
   bool use_dk = true;              // wave k-NN kernel starts from per-photon K-th bounds
-  DBuf qseg[2];  // K-best lists of the query-per-wave k-NN path
+  DBuf qseg[2];  // per list, [nprim + 1]: the sorted appends of primary b are [qseg[b], qseg[b + 1])
   size_t qcap_hint[2] = {0, 0};
   KeySortScratch keysort[2];
   int knn_kernel_kind = -1;  // -1 auto; run_knn lists the kinds
@@ -660,13 +676,12 @@ int set_map_device(gi_ctx *c, int mi, DBuf &dev, int64_t n) {
 // grow a device buffer to `want` bytes keeping its first `used` bytes
 hipError_t grow_keep(DBuf &b, size_t used, size_t want, hipStream_t st) {
   if (want <= b.cap && b.p) return hipSuccess;
-  DBuf nb;
+  TmpBuf nb;
   hipError_t e = nb.ensure(std::max(want, b.cap + b.cap / 2));
   if (e != hipSuccess) return e;
   if (used) e = hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  b.release();
-  b = nb;
+  std::swap<DBuf>(b, nb);  // the old buffer is freed with nb
   return e;
 }
 
@@ -903,6 +918,13 @@ hipError_t read_stats(gi_ctx *c, unsigned long long *out) {
   }
   return e;
 }
+// GI_KNN_DBG & 16: the k-NN kernels' phase counters of the counters read_stats summed, on stderr
+static void log_phase_cycles(const gi_ctx *c, const unsigned long long *s) {
+  if (!(c->knn_dbg & 16)) return;
+  fprintf(stderr, "[gi] k-NN phase cycles (sum over waves):");
+  for (int i = 0; i < 16; i++) fprintf(stderr, " %llu", s[ST_PHASE + i]);
+  fprintf(stderr, "\n");
+}
 
 // KnnArgs::general: 0 when the map's filter is the disk and no material a query can carry (kd or
 // the diffuse flag: queries sit on diffuse hits) has a specular term -- the device's test for the
@@ -945,14 +967,16 @@ KnnArgs knn_args(gi_ctx *c, int mi) {
   return k;
 }
 
+// the map a launch's arguments were made for (knn_args): 0 global, 1 caustic
+static int map_index(const KnnArgs &k) { return k.stat_off ? 1 : 0; }
+
 // Per-photon K-th distance bounds of map mi for this launch's K and r (KdView::dk): one
 // KNN_MODE_DK pass of the wave kernel with the photons themselves as queries, computed once
 // per map and (K, r). The wave kernel then starts each query from the bound of the photons in
 // its leaf instead of from r.
 int ensure_dk(gi_ctx *c, KnnArgs &k) {
-  MapExec &X = c->mx[k.stat_off ? 1 : 0];
-  int mi = k.stat_off ? 1 : 0;
-  DevMap &D = c->dmap[mi];
+  MapExec &X = c->mx[map_index(k)];
+  DevMap &D = c->dmap[map_index(k)];
   if (!c->use_dk || D.n == 0 || k.K <= 0) return GI_OK;
   if (D.dk_k != k.K || D.dk_r2 != k.r2f) {
     D.dk_k = -1;
@@ -981,15 +1005,13 @@ int ensure_dk(gi_ctx *c, KnnArgs &k) {
   return GI_OK;
 }
 
-// run a k-NN launch over nq queries (chunked when the heap lives in global scratch)
-int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
-  MapExec &X = c->mx[k.stat_off ? 1 : 0];
-  // Kernel choice (GI_KNN_KERNEL overrides; -1 = auto):
-  //   7  chunk kernel with lane select + per-lane fallback (K <= 64, estimates): the default
-  //   3  per-lane kernel, LDS heaps (K <= 128; list mode)
-  //   8  large-K chunk kernel + query-per-wave fallback (K > 64, estimates; needs dk bounds)
-  //   1  query-per-wave kernel (K + 64 <= 1024)
-  //   0  per-lane kernel with global-memory heaps (any K)
+// Kernel choice of a launch (GI_KNN_KERNEL overrides; -1 = auto):
+//   7  chunk kernel with lane select + per-lane fallback (K <= 64, estimates): the default
+//   3  per-lane kernel, LDS heaps (K <= 128; list mode)
+//   8  large-K chunk kernel + query-per-wave fallback (K > 64, estimates; needs dk bounds)
+//   1  query-per-wave kernel (K + 64 <= 1024)
+//   0  per-lane kernel with global-memory heaps (any K)
+static int knn_kind(const gi_ctx *c, const KnnArgs &k) {
   int kind = c->knn_kernel_kind;
   const bool list = k.mode == KNN_MODE_LIST, dkm = k.mode == KNN_MODE_DK;
   int auto_kind = (k.K <= 64) ? (list ? 3 : 7) : ((list || !c->use_dk) ? 1 : 8);
@@ -999,206 +1021,190 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
   if (kind == 8 && (list || dkm || k.K + 64 > 1024 || !c->use_dk)) kind = auto_kind == 8 ? 1 : auto_kind;
   if (kind == 3 && (size_t)k.K * 512 > 64 * 1024) kind = auto_kind;
   if (kind == 1 && k.K + 64 > 1024) kind = 0;
-  if (!dkm) c->last_kind[k.stat_off ? 1 : 0] = kind;
+  return kind;
+}
+
+// end of a launch on the map's stream: records ev1 and, when the caller times the launch, waits
+// for it and adds the time since ev0 to *ms
+static int knn_end(gi_ctx *c, MapExec &X, double *ms) {
+  HIPCHK(c, hipEventRecord(X.ev1, X.st));
+  if (ms) {
+    HIPCHK(c, hipEventSynchronize(X.ev1));
+    float t = 0;
+    HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
+    *ms += t;
+  }
+  return GI_OK;
+}
+
+// Makes F ready for what a chunk pass over nq queries hands on and points the pass's arguments
+// at it. Striped list (gi_knn_chunk.hip to_fallback): block b -> stripe b % FB_QS, at most 64
+// queries per chunk, ceil(chunks / grid) chunks per block.
+static int fb_prepare(gi_ctx *c, MapExec &X, FbList &F, int64_t nq, KnnArgs &k) {
+  int64_t chunks = (nq + 63) / 64;
+  int64_t grid = knn_chunk_grid(nq);
+  uint32_t cap_s = (uint32_t)(64 * ((chunks + grid - 1) / grid) * ((grid + FB_QS - 1) / FB_QS));
+  HIPCHK(c, F.list.ensure((size_t)FB_QS * cap_s * 4));
+  HIPCHK(c, F.dense.ensure((size_t)nq * 4 + 4));
+  HIPCHK(c, F.count.ensure(FB_QS * 32 * 4));
+  HIPCHK(c, hipMemsetAsync(F.count.p, 0, FB_QS * 32 * 4, X.st));
+  k.fb_list = F.list.as<uint32_t>();
+  k.fb_count = F.count.as<uint32_t>();
+  k.fb_cap_s = cap_s;
+  return GI_OK;
+}
+
+// Compacts what the pass with arguments k, over nq queries, handed on into F.dense and reads their
+// number back (one host synchronization); ev, when given, is recorded behind the compaction.
+static int fb_collect(gi_ctx *c, MapExec &X, FbList &F, const KnnArgs &k, int64_t nq,
+                      hipEvent_t ev, uint32_t *n) {
+  uint32_t *dense = F.dense.as<uint32_t>();
+  launch_fb_compact(k.fb_list, k.fb_count, k.fb_cap_s, dense, dense + nq, X.st);
+  HIPCHK(c, hipGetLastError());
+  if (ev) HIPCHK(c, hipEventRecord(ev, X.st));
+  HIPCHK(c, hipMemcpyAsync(n, dense + nq, 4, hipMemcpyDeviceToHost, X.st));
+  HIPCHK(c, hipStreamSynchronize(X.st));
+  return GI_OK;
+}
+
+// One kernel launch of a chunk pipeline over its arguments' queries, with the changes to them
+// that are its own; false: no instance of the kernel serves them.
+using KnnPass = std::function<bool(KnnArgs)>;
+
+// The launch sequence of kinds 7 and 8: a chunk pass over all queries, further chunk passes over
+// what the pass before handed on (the compacted lists keep each chunk's queries together, in
+// Morton order), and a last-resort kernel for what the last chunk pass hands on.
+struct ChunkPipeline {
+  int kind;
+  const char *first_label, *last_label;  // of the GI_LOG & 4 line
+  KnnPass first;
+  std::vector<KnnPass> more;
+  KnnPass last;
+};
+
+// k: the first pass's arguments, over nq queries, with X.fb[0] prepared for them (fb_prepare).
+// Every later pass gets k with the dense list of the pass before as its queries; pass i of `more`
+// writes X.fb[(i + 1) & 1] (ping-pong: a list is free once the pass behind it has read it).
+static int run_chunk_knn(gi_ctx *c, MapExec &X, const KnnArgs &k, int64_t nq, double *ms,
+                         const ChunkPipeline &P) {
+  HIPCHK(c, hipEventRecord(X.ev0, X.st));
+  if (!P.first(k)) return fail(c, GI_ERR_ARG, "k-NN launch: large-K chunk kernel unavailable");
+  HIPCHK(c, hipGetLastError());
+  uint32_t nfb = 0;
+  int rc = fb_collect(c, X, X.fb[0], k, nq, X.ev2, &nfb);
+  if (rc) return rc;
+  X.fb_total += nfb;
+  uint32_t rest = nfb;
+  const uint32_t *dense = X.fb[0].dense.as<uint32_t>();
+  bool ran_more = false;
+  for (size_t i = 0; i < P.more.size() && rest; i++) {
+    ran_more = true;
+    FbList &F = X.fb[(i + 1) & 1];
+    const uint32_t nin = rest;
+    KnnArgs s = k;
+    s.perm = dense;
+    s.nq = nin;
+    s.q0 = 0;
+    s.dbg &= ~16;
+    if ((rc = fb_prepare(c, X, F, nin, s))) return rc;
+    if (!P.more[i](s)) return fail(c, GI_ERR_ARG, "k-NN launch: large-K chunk kernel unavailable");
+    HIPCHK(c, hipGetLastError());
+    if ((rc = fb_collect(c, X, F, s, nin, nullptr, &rest))) return rc;
+    dense = F.dense.as<uint32_t>();
+  }
+  HIPCHK(c, hipEventRecord(X.ev3, X.st));
+  if (rest) {
+    KnnArgs f = k;
+    f.perm = dense;
+    f.nq = rest;
+    f.q0 = 0;
+    if (!P.last(f))
+      return fail(c, GI_ERR_ARG, "k-NN launch: unsupported estimate size for this kernel");
+    HIPCHK(c, hipGetLastError());
+  }
+  double t = 0;
+  if ((rc = knn_end(c, X, ms ? &t : nullptr))) return rc;
+  if (ms) {
+    float tf = 0, t2 = 0;
+    HIPCHK(c, hipEventElapsedTime(&tf, X.ev3, X.ev1));
+    HIPCHK(c, hipEventElapsedTime(&t2, X.ev2, X.ev3));
+    *ms += t;
+    const int mi = map_index(k);
+    c->fb_ms[mi] += tf;
+    c->fb_q[mi] += rest;
+    c->p2_ms[mi] += t2;
+    c->p2_q[mi] += ran_more ? nfb : 0;
+    if (c->knn_log)
+      fprintf(stderr, "[gi] knn map %d kind %d: nq %lld %s %.2f ms, second pass %u (%.2f ms), %s %u (%.2f ms)\n",
+              mi, P.kind, (long long)nq, P.first_label, (float)t - tf - t2, nfb, t2, P.last_label,
+              rest, tf);
+  }
+  return GI_OK;
+}
+
+// run a k-NN launch over nq queries (chunked when the heap lives in global scratch)
+int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
+  MapExec &X = c->mx[map_index(k)];
+  const hipStream_t st = X.st;
+  const int kind = knn_kind(c, k);
+  if (k.mode != KNN_MODE_DK) c->last_kind[map_index(k)] = kind;
   if (kind == 8) {
     // large-K chunk kernel, then the query-per-wave kernel on what it hands over
     int rc = ensure_dk(c, k);
     if (rc) return rc;
-    int64_t chunks = (nq + 63) / 64;
-    int64_t grid = knn_chunk_grid(nq);
-    uint32_t cap_s = (uint32_t)(64 * ((chunks + grid - 1) / grid) * ((grid + FB_QS - 1) / FB_QS));
-    HIPCHK(c, X.fb_list.ensure((size_t)FB_QS * cap_s * 4));
-    HIPCHK(c, X.fb_dense.ensure((size_t)nq * 4 + 4));
-    HIPCHK(c, X.fb_count.ensure(FB_QS * 32 * 4));
-    HIPCHK(c, hipMemsetAsync(X.fb_count.p, 0, FB_QS * 32 * 4, X.st));
     k.nq = nq;
     k.q0 = 0;
-    k.fb_list = X.fb_list.as<uint32_t>();
-    k.fb_count = X.fb_count.as<uint32_t>();
-    k.fb_cap_s = cap_s;
+    if ((rc = fb_prepare(c, X, X.fb[0], nq, k))) return rc;
     k.chunk_minsub = c->chunk_minsub_big;
     k.dk_exact = c->chunk_dk_exact ? 1 : 0;
-    HIPCHK(c, hipEventRecord(X.ev0, X.st));
-    if (!launch_knn_chunk_big(k, c->chunk_cap_big, X.st))
-      return fail(c, GI_ERR_ARG, "k-NN launch: large-K chunk kernel unavailable");
-    HIPCHK(c, hipGetLastError());
-    uint32_t *dense = X.fb_dense.as<uint32_t>();
-    launch_fb_compact(k.fb_list, k.fb_count, cap_s, dense, dense + nq, X.st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(X.ev2, X.st));
-    uint32_t nfb = 0;
-    HIPCHK(c, hipMemcpyAsync(&nfb, dense + nq, 4, hipMemcpyDeviceToHost, X.st));
-    HIPCHK(c, hipStreamSynchronize(X.st));
-    X.fb_total += nfb;
-    uint32_t nfb2 = nfb;
-    bool ran2 = false;
-    // further chunk passes over the overflowing chunks' queries, with more LDS candidates each
-    // (chunk_cap_big2: 1024 by default; chunk_cap_big3 > 0 adds a third); the compacted lists
-    // keep each chunk's queries together, in Morton order. What overflows the last one goes to
-    // the query-per-wave kernel. Pass i reads `dense` and writes the other list (ping-pong:
-    // the first pass's list is free once the second has read it).
-    const int caps2[2] = {c->chunk_cap_big2, c->chunk_cap_big3};
-    for (int pi = 0; pi < 2 && nfb2 && c->chunk_big2 && caps2[pi] > 0; pi++) {
-      ran2 = true;
-      const uint32_t nin = nfb2;
-      DBuf &L = pi == 0 ? X.fb_list2 : X.fb_list;
-      DBuf &Dn = pi == 0 ? X.fb_dense2 : X.fb_dense;
-      DBuf &Cn = pi == 0 ? X.fb_count2 : X.fb_count;
-      int64_t chunks2 = ((int64_t)nin + 63) / 64;
-      int64_t grid2 = knn_chunk_grid(nin);
-      uint32_t cap2 = (uint32_t)(64 * ((chunks2 + grid2 - 1) / grid2) * ((grid2 + FB_QS - 1) / FB_QS));
-      HIPCHK(c, L.ensure((size_t)FB_QS * cap2 * 4));
-      HIPCHK(c, Dn.ensure((size_t)nin * 4 + 4));
-      HIPCHK(c, Cn.ensure(FB_QS * 32 * 4));
-      HIPCHK(c, hipMemsetAsync(Cn.p, 0, FB_QS * 32 * 4, X.st));
-      KnnArgs s2 = k;
-      s2.perm = dense;
-      s2.nq = nin;
-      s2.q0 = 0;
-      s2.fb_list = L.as<uint32_t>();
-      s2.fb_count = Cn.as<uint32_t>();
-      s2.fb_cap_s = cap2;
-      s2.dbg &= ~16;
-      s2.chunk_minsub = c->chunk_minsub_big2;
-      if (!launch_knn_chunk_big(s2, caps2[pi], X.st))
-        return fail(c, GI_ERR_ARG, "k-NN launch: large-K chunk kernel unavailable");
-      HIPCHK(c, hipGetLastError());
-      dense = Dn.as<uint32_t>();
-      launch_fb_compact(s2.fb_list, s2.fb_count, cap2, dense, dense + nin, X.st);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(&nfb2, dense + nin, 4, hipMemcpyDeviceToHost, X.st));
-      HIPCHK(c, hipStreamSynchronize(X.st));
+    ChunkPipeline P{8, "chunk pass", "wave"};
+    P.first = [&](KnnArgs a) { return launch_knn_chunk_big(a, c->chunk_cap_big, st); };
+    // further chunk passes with more LDS candidates each (chunk_cap_big2: 1024 by default;
+    // chunk_cap_big3 > 0 adds a third)
+    const int caps[2] = {c->chunk_cap_big2, c->chunk_cap_big3};
+    for (int i = 0; i < 2 && c->chunk_big2 && caps[i] > 0; i++) {
+      const int cap = caps[i];
+      P.more.push_back([c, st, cap](KnnArgs a) {
+        a.chunk_minsub = c->chunk_minsub_big2;
+        return launch_knn_chunk_big(a, cap, st);
+      });
     }
-    HIPCHK(c, hipEventRecord(X.ev3, X.st));
-    if (nfb2) {
-      KnnArgs f = k;
-      f.perm = dense;
-      f.nq = nfb2;
-      f.q0 = 0;
-      if (!launch_knn_wave(f, c->wave_cap_mul, X.st))
-        return fail(c, GI_ERR_ARG, "k-NN launch: unsupported estimate size for this kernel");
-      HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipEventRecord(X.ev1, X.st));
-    if (ms) {
-      HIPCHK(c, hipEventSynchronize(X.ev1));
-      float t = 0, tf = 0, t2 = 0;
-      HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
-      HIPCHK(c, hipEventElapsedTime(&tf, X.ev3, X.ev1));
-      HIPCHK(c, hipEventElapsedTime(&t2, X.ev2, X.ev3));
-      *ms += t;
-      int mi = k.stat_off ? 1 : 0;
-      c->fb_ms[mi] += tf;
-      c->fb_q[mi] += nfb2;
-      c->p2_ms[mi] += t2;
-      c->p2_q[mi] += ran2 ? nfb : 0;
-      if (c->knn_log)
-        fprintf(stderr, "[gi] knn map %d kind 8: nq %lld chunk pass %.2f ms, second pass %u (%.2f ms), wave %u (%.2f ms)\n",
-                mi, (long long)nq, t - tf - t2, nfb, t2, nfb2, tf);
-    }
-    return GI_OK;
+    P.last = [&](KnnArgs a) { return launch_knn_wave(a, c->wave_cap_mul, st); };
+    return run_chunk_knn(c, X, k, nq, ms, P);
   }
   if (kind == 7) {
-    // chunk kernel, then the per-lane kernel on the chunks that overflowed its LDS gather
-    // striped fallback list (gi_knn_chunk.hip to_fallback): block b -> stripe b % FB_QS, at most
-    // 64 queries per chunk, ceil(chunks / grid) chunks per block
-    int64_t chunks = (nq + 63) / 64;
-    int64_t grid = knn_chunk_grid(nq);
-    uint32_t cap_s = (uint32_t)(64 * ((chunks + grid - 1) / grid) * ((grid + FB_QS - 1) / FB_QS));
-    HIPCHK(c, X.fb_list.ensure((size_t)FB_QS * cap_s * 4));
-    HIPCHK(c, X.fb_dense.ensure((size_t)nq * 4 + 4));
-    HIPCHK(c, X.fb_count.ensure(FB_QS * 32 * 4));
-    HIPCHK(c, hipMemsetAsync(X.fb_count.p, 0, FB_QS * 32 * 4, X.st));
+    // chunk kernel, then its 480-candidate second pass on the chunks that overflowed its LDS
+    // gather, then the query-per-wave (or per-lane) kernel on those that overflowed that
     k.nq = nq;
     k.q0 = 0;
-    k.fb_list = X.fb_list.as<uint32_t>();
-    k.fb_count = X.fb_count.as<uint32_t>();
-    k.fb_cap_s = cap_s;
+    int rc = fb_prepare(c, X, X.fb[0], nq, k);
+    if (rc) return rc;
     // per-photon K-th distance bounds: the fallback's starting bound; the chunk kernel's centre
     // bound uses them only with chunk_dk (else the exact d_K(c) gather)
     const float *fb_dk = nullptr;
     if (c->use_dk && k.mode != KNN_MODE_DK) {
-      int rc = ensure_dk(c, k);
-      if (rc) return rc;
+      if ((rc = ensure_dk(c, k))) return rc;
       fb_dk = k.map.dk;
       if (!c->chunk_dk) k.map.dk = nullptr;
     }
-    const int dbg0 = k.dbg;
-    if (c->chunk_fb_all) k.dbg |= 4;  // lane select skipped: all to the fallback
-    HIPCHK(c, hipEventRecord(X.ev0, X.st));
-    launch_knn_chunk(k, X.st);
-    k.dbg = dbg0;
-    HIPCHK(c, hipGetLastError());
-    uint32_t *dense = X.fb_dense.as<uint32_t>();
-    launch_fb_compact(k.fb_list, k.fb_count, cap_s, dense, dense + nq, X.st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(X.ev2, X.st));
-    uint32_t nfb = 0;
-    HIPCHK(c, hipMemcpyAsync(&nfb, dense + nq, 4, hipMemcpyDeviceToHost, X.st));
-    HIPCHK(c, hipStreamSynchronize(X.st));
-    X.fb_total += nfb;
-    uint32_t nfb2 = nfb;
-    bool ran2 = false;
-    if (nfb && c->chunk_lane2 && !c->chunk_fb_all) {
-      ran2 = true;
-      // second chunk pass, 480 LDS candidates, over the overflowing chunks' queries (the
-      // compacted list keeps each chunk's queries together, in Morton order)
-      int64_t chunks2 = ((int64_t)nfb + 63) / 64;
-      int64_t grid2 = knn_chunk_grid(nfb);
-      uint32_t cap2 = (uint32_t)(64 * ((chunks2 + grid2 - 1) / grid2) * ((grid2 + FB_QS - 1) / FB_QS));
-      HIPCHK(c, X.fb_list2.ensure((size_t)FB_QS * cap2 * 4));
-      HIPCHK(c, X.fb_dense2.ensure((size_t)nfb * 4 + 4));
-      HIPCHK(c, X.fb_count2.ensure(FB_QS * 32 * 4));
-      HIPCHK(c, hipMemsetAsync(X.fb_count2.p, 0, FB_QS * 32 * 4, X.st));
-      KnnArgs s2 = k;
-      s2.perm = dense;
-      s2.nq = nfb;
-      s2.q0 = 0;
-      s2.fb_list = X.fb_list2.as<uint32_t>();
-      s2.fb_count = X.fb_count2.as<uint32_t>();
-      s2.fb_cap_s = cap2;
-      s2.dbg &= ~16;
-      launch_knn_chunk2(s2, X.st);
-      HIPCHK(c, hipGetLastError());
-      dense = X.fb_dense2.as<uint32_t>();
-      launch_fb_compact(s2.fb_list, s2.fb_count, cap2, dense, dense + nfb, X.st);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(&nfb2, dense + nfb, 4, hipMemcpyDeviceToHost, X.st));
-      HIPCHK(c, hipStreamSynchronize(X.st));
-    }
-    HIPCHK(c, hipEventRecord(X.ev3, X.st));
-    if (nfb2) {
-      KnnArgs f = k;
-      f.perm = dense;
-      f.nq = nfb2;
-      f.q0 = 0;
-      f.map.dk = fb_dk;
-      if (c->fb_wave) {
-        if (!launch_knn_wave(f, c->wave_cap_mul, X.st))
-          return fail(c, GI_ERR_ARG, "k-NN launch: unsupported estimate size for this kernel");
-      } else {
-        launch_knn_lane(f, X.st);
-      }
-      HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipEventRecord(X.ev1, X.st));
-    if (ms) {
-      HIPCHK(c, hipEventSynchronize(X.ev1));
-      float t = 0, tf = 0, t2 = 0;
-      HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
-      HIPCHK(c, hipEventElapsedTime(&tf, X.ev3, X.ev1));
-      HIPCHK(c, hipEventElapsedTime(&t2, X.ev2, X.ev3));
-      *ms += t;
-      int mi = k.stat_off ? 1 : 0;
-      c->fb_ms[mi] += tf;
-      c->fb_q[mi] += nfb2;
-      c->p2_ms[mi] += t2;
-      c->p2_q[mi] += ran2 ? nfb : 0;
-      if (c->knn_log)
-        fprintf(stderr, "[gi] knn map %d kind 7: nq %lld chunk %.2f ms, second pass %u (%.2f ms), per-lane %u (%.2f ms)\n",
-                mi, (long long)nq, t - tf - t2, nfb, t2, nfb2, tf);
-    }
-    return GI_OK;
+    ChunkPipeline P{7, "chunk", "per-lane"};
+    P.first = [&](KnnArgs a) {
+      if (c->chunk_fb_all) a.dbg |= 4;  // lane select skipped: all to the fallback
+      launch_knn_chunk(a, st);
+      return true;
+    };
+    if (c->chunk_lane2 && !c->chunk_fb_all)
+      P.more.push_back([st](KnnArgs a) {
+        launch_knn_chunk2(a, st);
+        return true;
+      });
+    P.last = [&](KnnArgs a) {
+      a.map.dk = fb_dk;
+      if (c->fb_wave) return launch_knn_wave(a, c->wave_cap_mul, st);
+      launch_knn_lane(a, st);
+      return true;
+    };
+    return run_chunk_knn(c, X, k, nq, ms, P);
   }
   if (kind == 3) {
     k.nq = nq;
@@ -1206,14 +1212,7 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
     HIPCHK(c, hipEventRecord(X.ev0, X.st));
     launch_knn_lane(k, X.st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(X.ev1, X.st));
-    if (ms) {
-      HIPCHK(c, hipEventSynchronize(X.ev1));
-      float t = 0;
-      HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
-      *ms += t;
-    }
-    return GI_OK;
+    return knn_end(c, X, ms);
   }
   if (kind == 1) {
     // one query per wave; the search writes per-query K-best lists in list / DK mode (and when
@@ -1239,14 +1238,7 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
     if (!launch_knn_wave(k, c->wave_cap_mul, X.st))
       return fail(c, GI_ERR_ARG, "k-NN launch: unsupported estimate size for this kernel");
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(X.ev1, X.st));
-    if (ms) {
-      HIPCHK(c, hipEventSynchronize(X.ev1));
-      float t = 0;
-      HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
-      *ms += t;
-    }
-    return GI_OK;
+    return knn_end(c, X, ms);
   }
   // kind 0: per-lane heaps in global scratch, launched in slices of 2^20 queries
   const int64_t CH = (int64_t)(1 << 20);
@@ -1265,13 +1257,8 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
     HIPCHK(c, hipEventRecord(X.ev0, X.st));
     launch_knn(a, X.st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(X.ev1, X.st));
-    if (ms) {
-      HIPCHK(c, hipEventSynchronize(X.ev1));
-      float t = 0;
-      HIPCHK(c, hipEventElapsedTime(&t, X.ev0, X.ev1));
-      *ms += t;
-    }
+    int rc = knn_end(c, X, ms);
+    if (rc) return rc;
   }
   return GI_OK;
 }
@@ -1916,8 +1903,9 @@ static void release_scratch(gi_ctx *c) {
   for (auto &b : c->peer_pix) b.release();
   for (int m = 0; m < 2; m++) {
     MapExec &X = c->mx[m];
-    DBuf *xb[] = {&X.list_idx, &X.list_d2, &X.list_n, &X.gheap_d2, &X.gheap_idx, &X.fb_list, &X.fb_count,
-                  &X.fb_dense, &X.fb_list2, &X.fb_count2, &X.fb_dense2, &X.dk_q};
+    DBuf *xb[] = {&X.list_idx, &X.list_d2, &X.list_n, &X.gheap_d2, &X.gheap_idx, &X.fb[0].list,
+                  &X.fb[0].count, &X.fb[0].dense, &X.fb[1].list, &X.fb[1].count, &X.fb[1].dense,
+                  &X.dk_q};
     for (DBuf *b : xb) b->release();
     sort_scratch_release(X.sorter);
   }
@@ -2163,26 +2151,26 @@ int gi_map_photons(gi_ctx *c, gi_photon_stats *st) {
       q[4 * i + 2] = H.storage[i].pos[2];
       q[4 * i + 3] = 0;
     }
-    DBuf dq, dout;
-    HIPCHK(c, upload(dq, q.data(), q.size() * 4, c->stream));
-    HIPCHK(c, dout.ensure((size_t)n * 24));
-    KnnArgs k = knn_args(c, GI_MAP_GLOBAL);
-    k.mode = KNN_MODE_IRRADIANCE;
-    k.qpos = dq.as<float4>();
-    k.out = dout.as<double>();
-    k.stats = nullptr;
-    // Morton order, as for the render's queries: the chunk kernel's 64-query chunks are then
-    // spatial neighbourhoods (emission order scatters them over the scene)
-    uint32_t *iperm = nullptr;
-    HIPCHK(c, morton_order(dq.as<float4>(), n, c->sbmin, c->sbmax, c->mx[0].sorter, &iperm, c->stream));
-    k.perm = iperm;
-    rc = run_knn(c, k, n, nullptr);
-    if (rc) return rc;
     std::vector<double> irr(3 * n);
-    HIPCHK(c, hipMemcpyAsync(irr.data(), dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dq.release();
-    dout.release();
+    {
+      TmpBuf dq, dout;  // freed before the map is set again
+      HIPCHK(c, upload(dq, q.data(), q.size() * 4, c->stream));
+      HIPCHK(c, dout.ensure((size_t)n * 24));
+      KnnArgs k = knn_args(c, GI_MAP_GLOBAL);
+      k.mode = KNN_MODE_IRRADIANCE;
+      k.qpos = dq.as<float4>();
+      k.out = dout.as<double>();
+      k.stats = nullptr;
+      // Morton order, as for the render's queries: the chunk kernel's 64-query chunks are then
+      // spatial neighbourhoods (emission order scatters them over the scene)
+      uint32_t *iperm = nullptr;
+      HIPCHK(c, morton_order(dq.as<float4>(), n, c->sbmin, c->sbmax, c->mx[0].sorter, &iperm, c->stream));
+      k.perm = iperm;
+      rc = run_knn(c, k, n, nullptr);
+      if (rc) return rc;
+      HIPCHK(c, hipMemcpyAsync(irr.data(), dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     std::vector<gi_photon> cached = H.storage;
     for (int64_t i = 0; i < n; i++) {
       double col[3];
@@ -2280,17 +2268,24 @@ static int render_common(gi_ctx *c, int aa, int w, int h, const std::vector<int3
   size_t npx = (size_t)w * h * 3;
   HIPCHK(c, c->rgbf.ensure(npx * 4));
   HIPCHK(c, c->rgb8.ensure(npx));
-  if (keep_rgbf && rgbf) {
-    HIPCHK(c, hipMemcpyAsync(c->rgbf.p, rgbf, npx * 4, hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIPCHK(c, hipMemsetAsync(c->rgbf.p, 0, npx * 4, c->stream));
-  }
-  HIPCHK(c, hipMemsetAsync(c->rgb8.p, 0, npx, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, ST_BYTES, c->stream));
-  c->fb_ms[0] = c->fb_ms[1] = 0;
-  c->fb_q[0] = c->fb_q[1] = 0;
-  c->p2_ms[0] = c->p2_ms[1] = 0;
-  c->p2_q[0] = c->p2_q[1] = 0;
+  // the frame's device images (the caller's floats kept, or cleared), the counters and the
+  // k-NN pass counters, as they are before a frame's first batch
+  auto reset_frame = [&]() -> int {
+    if (keep_rgbf && rgbf) {
+      HIPCHK(c, hipMemcpyAsync(c->rgbf.p, rgbf, npx * 4, hipMemcpyHostToDevice, c->stream));
+    } else {
+      HIPCHK(c, hipMemsetAsync(c->rgbf.p, 0, npx * 4, c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(c->rgb8.p, 0, npx, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, ST_BYTES, c->stream));
+    c->fb_ms[0] = c->fb_ms[1] = 0;
+    c->fb_q[0] = c->fb_q[1] = 0;
+    c->p2_ms[0] = c->p2_ms[1] = 0;
+    c->p2_q[0] = c->p2_q[1] = 0;
+    return GI_OK;
+  };
+  rc = reset_frame();
+  if (rc) return rc;
   c->last_kind[0] = c->last_kind[1] = -1;
   gi_render_stats local;
   unsigned long long s[ST_COUNT];
@@ -2308,26 +2303,13 @@ static int render_common(gi_ctx *c, int aa, int w, int h, const std::vector<int3
     fprintf(stderr, "[gi] %llu k-NN queries needed the general estimate form; re-rendering with "
             "the general k-NN instances\n", s[ST_GEN_MISS]);
     c->knn_general_mode = 1;
-    if (keep_rgbf && rgbf) {
-      HIPCHK(c, hipMemcpyAsync(c->rgbf.p, rgbf, npx * 4, hipMemcpyHostToDevice, c->stream));
-    } else {
-      HIPCHK(c, hipMemsetAsync(c->rgbf.p, 0, npx * 4, c->stream));
-    }
-    HIPCHK(c, hipMemsetAsync(c->rgb8.p, 0, npx, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, ST_BYTES, c->stream));
-    c->fb_ms[0] = c->fb_ms[1] = 0;
-    c->fb_q[0] = c->fb_q[1] = 0;
-    c->p2_ms[0] = c->p2_ms[1] = 0;
-    c->p2_q[0] = c->p2_q[1] = 0;
+    rc = reset_frame();
+    if (rc) return rc;
   }
   if (rgbf) HIPCHK(c, hipMemcpyAsync(rgbf, c->rgbf.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
   if (rgb8) HIPCHK(c, hipMemcpyAsync(rgb8, c->rgb8.p, npx, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->knn_dbg & 16) {
-    fprintf(stderr, "[gi] k-NN phase cycles (sum over waves):");
-    for (int i = 0; i < 16; i++) fprintf(stderr, " %llu", s[ST_PHASE + i]);
-    fprintf(stderr, "\n");
-  }
+  log_phase_cycles(c, s);
   if (st) {
     st->screen_rays = s[ST_RAY];
     st->shadow_rays = s[ST_SHADOW];
@@ -3035,7 +3017,7 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
     pix[2 * p] = (int32_t)(p % w);
     pix[2 * p + 1] = (int32_t)(p / w);
   }
-  DBuf prim, pixels, frame, acc, part;
+  TmpBuf prim, pixels, frame, acc, part;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
   auto run = [&]() -> hipError_t {
@@ -3097,7 +3079,6 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
   (void)hipStreamSynchronize(c->stream);
   if (e0) hipEventDestroy(e0);
   if (e1) hipEventDestroy(e1);
-  for (DBuf *b : {&prim, &pixels, &frame, &acc, &part}) b->release();
   HIPCHK(c, e);
   return GI_OK;
 }
@@ -3134,7 +3115,7 @@ int gi_estimate_radiance_batch(gi_ctx *c, int map, int64_t n, const gi_radiance_
       qs[i].w[j] = 1.0;
     }
   }
-  DBuf dm, dq, ds, dout, dn, dmd;
+  TmpBuf dm, dq, ds, dout, dn, dmd;
   HIPCHK(c, upload(dm, mats.data(), mats.size() * sizeof(DMaterial), c->stream));
   HIPCHK(c, upload(dq, qp.data(), qp.size() * 4, c->stream));
   HIPCHK(c, upload(ds, qs.data(), qs.size() * sizeof(QShade), c->stream));
@@ -3172,8 +3153,6 @@ int gi_estimate_radiance_batch(gi_ctx *c, int map, int64_t n, const gi_radiance_
   if (nfound) HIPCHK(c, hipMemcpyAsync(nfound, dn.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   if (maxd2) HIPCHK(c, hipMemcpyAsync(maxd2, dmd.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  DBuf *bs[] = {&dm, &dq, &ds, &dout, &dn, &dmd};
-  for (DBuf *b : bs) b->release();
   return GI_OK;
 }
 
@@ -3185,7 +3164,7 @@ int gi_knn_batch(gi_ctx *c, int map, int64_t n, const double *pts, int K, double
   std::vector<float> qp(4 * n, 0.0f);
   for (int64_t i = 0; i < n; i++)
     for (int j = 0; j < 3; j++) qp[4 * i + j] = (float)pts[3 * i + j];
-  DBuf dq, di, dd, dn;
+  TmpBuf dq, di, dd, dn;
   HIPCHK(c, upload(dq, qp.data(), qp.size() * 4, c->stream));
   HIPCHK(c, di.ensure((size_t)n * K * 4));
   HIPCHK(c, dd.ensure((size_t)n * K * 4));
@@ -3210,7 +3189,6 @@ int gi_knn_batch(gi_ctx *c, int map, int64_t n, const double *pts, int K, double
   // kd order -> storage (emission) order indices
   const auto &perm = c->hmap[map].perm;
   for (size_t i = 0; i < idx.size(); i++) idx_out[i] = idx[i] >= 0 ? perm[idx[i]] : -1;
-  dq.release(); di.release(); dd.release(); dn.release();
   return GI_OK;
 }
 
@@ -3234,7 +3212,7 @@ int gi_knn_bench(gi_ctx *c, int map, int64_t n, const double *pts, const double 
     }
   }
   KnnArgs k = knn_args(c, map);
-  DBuf dq, ds, dout, di, dd, dn;
+  TmpBuf dq, ds, dout, di, dd, dn;
   HIPCHK(c, upload(dq, qp.data(), qp.size() * 4, c->stream));
   HIPCHK(c, upload(ds, qs.data(), qs.size() * sizeof(QShade), c->stream));
   HIPCHK(c, dout.ensure((size_t)n * 24));
@@ -3272,11 +3250,7 @@ int gi_knn_bench(gi_ctx *c, int map, int64_t n, const double *pts, const double 
   HIPCHK(c, read_stats(c, st));
   // a measurement over wrong (NaN) estimates would be meaningless
   if (st[ST_GEN_MISS]) return fail(c, GI_ERR_STATE, "k-NN bench: queries needed the general estimate form");
-  if (c->knn_dbg & 16) {
-    fprintf(stderr, "[gi] k-NN phase cycles (sum over waves):");
-    for (int i = 0; i < 16; i++) fprintf(stderr, " %llu", st[ST_PHASE + i]);
-    fprintf(stderr, "\n");
-  }
+  log_phase_cycles(c, st);
   if (ms_out) *ms_out = ms / iters;
   int so = map * ST_KNN_MAP;
   double nqd = (double)std::max<unsigned long long>(1, st[ST_KNN + so]);
@@ -3289,7 +3263,7 @@ int gi_math_probe(gi_ctx *c, int fn, int64_t n, const double *x, const double *y
   if (!c || n < 0 || fn < 0 || fn > 7 || (n > 0 && (!x || !y || !out))) return GI_ERR_ARG;
   if (n == 0) return GI_OK;
   DeviceScope scope(c->device);
-  DBuf dx, dy, dout;
+  TmpBuf dx, dy, dout;
   HIPCHK(c, upload(dx, x, (size_t)n * 8, c->stream));
   HIPCHK(c, upload(dy, y, (size_t)n * 8, c->stream));
   HIPCHK(c, dout.ensure((size_t)n * 8));
@@ -3297,9 +3271,6 @@ int gi_math_probe(gi_ctx *c, int fn, int64_t n, const double *x, const double *y
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dx.release();
-  dy.release();
-  dout.release();
   return GI_OK;
 }
 
@@ -3308,7 +3279,7 @@ int gi_intersect_batch(gi_ctx *c, int64_t n, const double *org, const double *di
   if (!c) return GI_ERR_ARG;
   if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded");
   if (n == 0) return GI_OK;
-  DBuf dorg, ddir, dhit, dt, dp, dn, dm;
+  TmpBuf dorg, ddir, dhit, dt, dp, dn, dm;
   HIPCHK(c, upload(dorg, org, (size_t)n * 24, c->stream));
   HIPCHK(c, upload(ddir, dir, (size_t)n * 24, c->stream));
   HIPCHK(c, dhit.ensure((size_t)n * 4));
@@ -3325,8 +3296,6 @@ int gi_intersect_batch(gi_ctx *c, int64_t n, const double *org, const double *di
   HIPCHK(c, hipMemcpyAsync(normal, dn.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(material, dm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  DBuf *bs[] = {&dorg, &ddir, &dhit, &dt, &dp, &dn, &dm};
-  for (DBuf *b : bs) b->release();
   return GI_OK;
 }
 
