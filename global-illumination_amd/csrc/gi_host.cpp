@@ -451,12 +451,14 @@ struct gi_ctx {
   // {m, M2} (six doubles per pixel), rad_samples the samples when the caller asked for them
   bool rad_on = false, rad_want_samples = false;
   DBuf rad_frame, rad_samples, rad_mean, rad_var;
-  // accumulator over passes (gi_accum_*): {mu, A} per pixel and one sample count for the frame;
-  // state of the context, kept by gi_release_scratch
-  DBuf acc, acc_part;
+  // accumulator over passes (gi_accum_*): {mu, A} per pixel and channel (acc) and one sample
+  // count per pixel (acc_cnt); state of the context, kept by gi_release_scratch. While only
+  // whole-frame passes were folded (acc_uniform) every count is acc_n.
+  DBuf acc, acc_cnt, acc_part;
   int acc_w = 0, acc_h = 0;
   int64_t acc_n = 0;
-  bool acc_valid = false;
+  bool acc_valid = false, acc_uniform = true;
+  DBuf tile_err, tile_nmin, tile_mask;  // adaptive passes: per tile error, smallest count, mask
   DBuf tm_in, tm_out;             // gi_tonemap
 };
 
@@ -1895,7 +1897,7 @@ static void release_scratch(gi_ctx *c) {
                   &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids,
                   &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
                   &c->dn_img[1], &c->rad_frame, &c->rad_samples, &c->rad_mean, &c->rad_var,
-                  &c->acc_part, &c->tm_in, &c->tm_out};
+                  &c->acc_part, &c->tile_err, &c->tile_nmin, &c->tile_mask, &c->tm_in, &c->tm_out};
   for (DBuf *b : bufs) b->release();
   std::vector<gi_ray>().swap(c->ray_stage);
   std::vector<uint64_t>().swap(c->id_stage);
@@ -1944,7 +1946,7 @@ void gi_destroy(gi_ctx *c) {
   hipSetDevice(c->device);
   release_scratch(c);
   DBuf *bufs[] = {&c->d_nodes, &c->d_elems, &c->d_shapes, &c->d_tris, &c->d_bvh, &c->d_mats,
-                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount, &c->acc};
+                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount, &c->acc, &c->acc_cnt};
   for (DBuf *b : bufs) b->release();
   for (int m = 0; m < 2; m++) {
     MapExec &X = c->mx[m];
@@ -2791,8 +2793,11 @@ int gi_denoise(gi_ctx *c, int w, int h, const float *rgbf, const gi_pixel_featur
 // One render with the radiance reduction on: c->rad_frame then holds the finished pass {m, M2}
 // (written once per pixel by the render that completed: a re-render after ST_GEN_MISS overwrites
 // every pixel, a batch re-run under the slot guard never reached its reduction).
+// pix (camera passes only): render these output pixels instead of the whole frame; rad_frame keeps
+// what it held at the others.
 static int radiance_pass(gi_ctx *c, int aa, int w, int h, bool want_samples, gi_render_stats *st,
-                         const RaySrc *rsrc, int64_t *S_out) {
+                         const RaySrc *rsrc, int64_t *S_out,
+                         const std::vector<int32_t> *pix = nullptr) {
   hipSetDevice(c->device);
   int rc = check_ready(c);
   if (rc) return rc;
@@ -2805,15 +2810,17 @@ static int radiance_pass(gi_ctx *c, int aa, int w, int h, bool want_samples, gi_
   if (want_samples) HIPCHK(c, c->rad_samples.ensure(npix * (size_t)S * 24));
   c->rad_want_samples = want_samples;
   c->rad_on = true;
-  rc = render_frame(c, aa, w, h, nullptr, nullptr, st, rsrc);
+  rc = pix ? render_common(c, aa, w, h, *pix, nullptr, nullptr, st, false)
+           : render_frame(c, aa, w, h, nullptr, nullptr, st, rsrc);
   c->rad_on = false;
   *S_out = S;
   return rc;
 }
 
-// {m, M2} of n samples per pixel -> host float mean / variance of the mean (either may be null)
+// {m, M2} of n samples per pixel (counts: of counts[p], the accumulator's) -> host float mean /
+// variance of the mean (either may be null)
 static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n, float *mean,
-                            float *variance) {
+                            float *variance, const int64_t *counts = nullptr) {
   if (!mean && !variance) return GI_OK;
   HIPCHK(c, c->rad_mean.ensure(npix * 12));
   HIPCHK(c, c->rad_var.ensure(npix * 12));
@@ -2821,6 +2828,7 @@ static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n
   memset(&a, 0, sizeof a);
   a.npix = (int64_t)npix;
   a.n = n;
+  a.counts = counts;
   a.frame = (const double *)frame.p;
   a.mean = mean ? c->rad_mean.as<float>() : nullptr;
   a.variance = variance ? c->rad_var.as<float>() : nullptr;
@@ -2888,11 +2896,14 @@ int gi_accum_reset(gi_ctx *c, int w, int h) {
   c->acc_valid = false;
   const size_t npix = (size_t)w * h;
   HIPCHK(c, c->acc.ensure(npix * 48));
+  HIPCHK(c, c->acc_cnt.ensure(npix * 8));
   HIPCHK(c, hipMemsetAsync(c->acc.p, 0, npix * 48, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->acc_cnt.p, 0, npix * 8, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->acc_w = w;
   c->acc_h = h;
   c->acc_n = 0;
+  c->acc_uniform = true;
   c->acc_valid = true;
   return GI_OK;
 }
@@ -2908,14 +2919,14 @@ static int accum_pass(gi_ctx *c, int aa, const RaySrc *rsrc, gi_render_stats *st
   AccumArgs a;
   memset(&a, 0, sizeof a);
   a.npix = (int64_t)c->acc_w * c->acc_h;
-  a.N = c->acc_n;
   a.S = S;
   a.pass = c->rad_frame.as<double>();
   a.acc = c->acc.as<double>();
+  a.counts = c->acc_cnt.as<int64_t>();
   launch_accum_merge(a, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->acc_n += S;
+  c->acc_n += S;  // every pixel's count while acc_uniform, else unused
   return GI_OK;
 }
 
@@ -2936,6 +2947,224 @@ int gi_accum_add_rays(gi_ctx *c, int spp, const gi_ray *rays, const uint64_t *id
   return accum_pass(c, 0, &src, st);
 }
 
+// smallest and summed per-pixel sample count of the accumulator (either output optional)
+static int count_stats(gi_ctx *c, int64_t *smallest, int64_t *total) {
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  const size_t nb = (npix + 255) / 256;
+  HIPCHK(c, c->acc_part.ensure(nb * 16));
+  CountArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = (int64_t)npix;
+  a.counts = c->acc_cnt.as<int64_t>();
+  a.partial = c->acc_part.as<int64_t>();
+  launch_count_stats(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  std::vector<int64_t> part(nb * 2);
+  HIPCHK(c, hipMemcpyAsync(part.data(), c->acc_part.p, nb * 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int64_t mn = part[0], sum = 0;
+  for (size_t b = 0; b < nb; b++) {
+    mn = std::min(mn, part[2 * b]);
+    sum += part[2 * b + 1];
+  }
+  if (smallest) *smallest = mn;
+  if (total) *total = sum;
+  return GI_OK;
+}
+
+int gi_accum_get_counts(gi_ctx *c, int64_t *counts, int64_t *total) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  if (counts) {
+    HIPCHK(c, hipMemcpyAsync(counts, c->acc_cnt.p, npix * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (total) return count_stats(c, nullptr, total);
+  return GI_OK;
+}
+
+// ---- adaptive passes (gi.h "adaptive passes"; tile_error_kernel, tile_select_kernel) ----------
+void gi_adaptive_params_default(gi_adaptive_params *p) {
+  p->tile_px = 8;
+  p->min_samples = 8;
+  p->max_samples = 0;
+  p->dilate = 1;
+  p->threshold = 0.02;
+}
+
+static int check_accum(gi_ctx *c) {
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
+  return GI_OK;
+}
+
+static int check_adaptive(gi_ctx *c, const gi_adaptive_params *p) {
+  if (!p) return fail(c, GI_ERR_ARG, "adaptive: null parameters");
+  if (p->tile_px < 4 || p->tile_px > 64) return fail(c, GI_ERR_ARG, "adaptive: tile_px outside 4..64");
+  if (p->min_samples < 0 || p->max_samples < 0)
+    return fail(c, GI_ERR_ARG, "adaptive: negative min_samples or max_samples");
+  if (p->dilate != 0 && p->dilate != 1) return fail(c, GI_ERR_ARG, "adaptive: dilate must be 0 or 1");
+  if (!std::isfinite(p->threshold) || p->threshold < 0.0)
+    return fail(c, GI_ERR_ARG, "adaptive: threshold must be finite and not negative");
+  return GI_OK;
+}
+
+// pixels of the tile mask's active tiles inside the w x h frame
+static int64_t mask_pixels(int w, int h, int tile, const uint8_t *mask, int64_t *tiles) {
+  const int tx = (w + tile - 1) / tile, ty = (h + tile - 1) / tile;
+  int64_t n = 0, nt = 0;
+  for (int t = 0; t < tx * ty; t++) {
+    if (!mask[t]) continue;
+    const int x0 = (t % tx) * tile, y0 = (t / tx) * tile;
+    n += (int64_t)(std::min(w, x0 + tile) - x0) * (std::min(h, y0 + tile) - y0);
+    nt++;
+  }
+  if (tiles) *tiles = nt;
+  return n;
+}
+
+// the selection into mask (host, one byte per tile); tile_error (host, optional)
+static int accum_select(gi_ctx *c, const gi_adaptive_params *p, std::vector<uint8_t> &mask,
+                        double *tile_error) {
+  DeviceScope dev(c->device);
+  const int T = p->tile_px;
+  const int tx = (c->acc_w + T - 1) / T, ty = (c->acc_h + T - 1) / T;
+  const size_t nt = (size_t)tx * ty;
+  HIPCHK(c, c->tile_err.ensure(nt * 8));
+  HIPCHK(c, c->tile_nmin.ensure(nt * 8));
+  HIPCHK(c, c->tile_mask.ensure(nt));
+  TileArgs a;
+  memset(&a, 0, sizeof a);
+  a.width = c->acc_w;
+  a.height = c->acc_h;
+  a.T = T;
+  a.tiles_x = tx;
+  a.tiles_y = ty;
+  a.acc = c->acc.as<double>();
+  a.counts = c->acc_cnt.as<int64_t>();
+  a.tile_error = c->tile_err.as<double>();
+  a.tile_nmin = c->tile_nmin.as<int64_t>();
+  launch_tile_error(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  SelectArgs s;
+  memset(&s, 0, sizeof s);
+  s.tiles_x = tx;
+  s.tiles_y = ty;
+  s.dilate = p->dilate;
+  s.min_samples = p->min_samples;
+  s.max_samples = p->max_samples;
+  s.threshold = p->threshold;
+  s.tile_error = a.tile_error;
+  s.tile_nmin = a.tile_nmin;
+  s.mask = c->tile_mask.as<uint8_t>();
+  launch_tile_select(s, c->stream);
+  HIPCHK(c, hipGetLastError());
+  mask.resize(nt);
+  HIPCHK(c, hipMemcpyAsync(mask.data(), c->tile_mask.p, nt, hipMemcpyDeviceToHost, c->stream));
+  if (tile_error)
+    HIPCHK(c, hipMemcpyAsync(tile_error, c->tile_err.p, nt * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+int gi_accum_select(gi_ctx *c, const gi_adaptive_params *p, uint8_t *mask, double *tile_error,
+                    int64_t *active_tiles, int64_t *active_pixels) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (!rc) rc = check_adaptive(c, p);
+  if (rc) return rc;
+  std::vector<uint8_t> m;
+  rc = accum_select(c, p, m, tile_error);
+  if (rc) return rc;
+  if (mask) memcpy(mask, m.data(), m.size());
+  int64_t nt = 0;
+  const int64_t np = mask_pixels(c->acc_w, c->acc_h, p->tile_px, m.data(), &nt);
+  if (active_tiles) *active_tiles = nt;
+  if (active_pixels) *active_pixels = np;
+  return GI_OK;
+}
+
+// one camera pass over the mask's tiles: the list is built on the host like a tile shard's
+// (shard_pixels: tiles in order, rows inside a tile), rendered, and folded into its pixels only
+static int accum_add_tiles(gi_ctx *c, int aa, int tile, const uint8_t *mask, int64_t *active_pixels,
+                           gi_render_stats *st) {
+  if (aa < 0 || aa > 15) return fail(c, GI_ERR_ARG, "bad image size");
+  const int w = c->acc_w, h = c->acc_h;
+  const int tx = (w + tile - 1) / tile, ty = (h + tile - 1) / tile;
+  std::vector<int32_t> pix;
+  pix.reserve((size_t)mask_pixels(w, h, tile, mask, nullptr) * 2);
+  for (int t = 0; t < tx * ty; t++) {
+    if (!mask[t]) continue;
+    const int x0 = (t % tx) * tile, y0 = (t / tx) * tile;
+    for (int y = y0; y < std::min(h, y0 + tile); y++)
+      for (int x = x0; x < std::min(w, x0 + tile); x++) {
+        pix.push_back(x);
+        pix.push_back(y);
+      }
+  }
+  const int64_t n = (int64_t)pix.size() / 2;
+  if (active_pixels) *active_pixels = n;
+  if (n == 0) {  // nothing to render, nothing launched
+    if (st) memset(st, 0, sizeof *st);
+    return GI_OK;
+  }
+  // render_pixels sizes its batches by the largest queries per primary sample seen so far. That
+  // rate was measured on whole frames and is low for a list made of the expensive tiles, so it is
+  // measured again on this list (as after gi_set_camera) and the frames' rate put back afterwards.
+  const double frame_rate = c->q_per_prim;
+  c->q_per_prim = 0.0;
+  int64_t S = 0;
+  int rc = radiance_pass(c, aa, w, h, false, st, nullptr, &S, &pix);
+  c->q_per_prim = frame_rate;
+  if (rc) return rc;
+  AccumArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = n;
+  a.S = S;
+  a.pass = c->rad_frame.as<double>();
+  a.acc = c->acc.as<double>();
+  a.counts = c->acc_cnt.as<int64_t>();
+  a.pixels = c->pixels.as<int2>();  // the list as render_pixels uploaded it
+  a.width = w;
+  launch_accum_merge(a, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n == (int64_t)w * h)
+    c->acc_n += S;
+  else
+    c->acc_uniform = false;
+  return GI_OK;
+}
+
+int gi_accum_add_tiles(gi_ctx *c, int aa, int tile_px, const uint8_t *mask, int64_t *active_pixels,
+                       gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (rc) return rc;
+  if (tile_px < 4 || tile_px > 64) return fail(c, GI_ERR_ARG, "adaptive: tile_px outside 4..64");
+  if (!mask) return fail(c, GI_ERR_ARG, "adaptive: null tile mask");
+  return accum_add_tiles(c, aa, tile_px, mask, active_pixels, st);
+}
+
+int gi_accum_add_adaptive(gi_ctx *c, int aa, const gi_adaptive_params *p, uint8_t *mask,
+                          int64_t *active_pixels, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (!rc) rc = check_adaptive(c, p);
+  if (rc) return rc;
+  if (aa < 0 || aa > 15) return fail(c, GI_ERR_ARG, "bad image size");
+  std::vector<uint8_t> m;
+  rc = accum_select(c, p, m, nullptr);
+  if (rc) return rc;
+  if (mask) memcpy(mask, m.data(), m.size());
+  return accum_add_tiles(c, aa, p->tile_px, m.data(), active_pixels, st);
+}
+
 int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, double *noise) {
   if (!c) return GI_ERR_ARG;
   if (!c->peers.empty())
@@ -2943,15 +3172,21 @@ int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, dou
   if (!c->acc_valid) return fail(c, GI_ERR_STATE, "no accumulator (gi_accum_reset)");
   DeviceScope dev(c->device);
   const size_t npix = (size_t)c->acc_w * c->acc_h;
-  if (nsamples) *nsamples = c->acc_n;
-  int rc = radiance_resolve(c, c->acc, npix, c->acc_n, mean, variance);
+  if (nsamples) {
+    *nsamples = c->acc_n;
+    if (!c->acc_uniform) {
+      int rc = count_stats(c, nsamples, nullptr);
+      if (rc) return rc;
+    }
+  }
+  int rc = radiance_resolve(c, c->acc, npix, 0, mean, variance, c->acc_cnt.as<int64_t>());
   if (rc || !noise) return rc;
   const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
   HIPCHK(c, c->acc_part.ensure(nb * 8));
   NoiseArgs a;
   memset(&a, 0, sizeof a);
   a.npix = (int64_t)npix;
-  a.n = c->acc_n;
+  a.counts = c->acc_cnt.as<int64_t>();
   a.acc = c->acc.as<double>();
   a.partial = c->acc_part.as<double>();
   launch_accum_noise(a, c->stream);
@@ -3017,7 +3252,7 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
     pix[2 * p] = (int32_t)(p % w);
     pix[2 * p + 1] = (int32_t)(p / w);
   }
-  TmpBuf prim, pixels, frame, acc, part;
+  TmpBuf prim, pixels, frame, acc, cnt, part;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
   auto run = [&]() -> hipError_t {
@@ -3027,6 +3262,9 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
     if ((e = frame.ensure(npix * 48)) != hipSuccess) return e;
     if ((e = acc.ensure(npix * 48)) != hipSuccess) return e;
     if ((e = part.ensure(nb * 8)) != hipSuccess) return e;
+    if ((e = cnt.ensure(npix * 8)) != hipSuccess) return e;
+    // counts of bytes 0x01 (7.2e16 samples): the merge's general branch, the noise's n >= 2
+    if ((e = hipMemsetAsync(cnt.p, 0x01, npix * 8, c->stream)) != hipSuccess) return e;
     // bytes 0x3f: every double is 4.7e-4
     if ((e = hipMemsetAsync(prim.p, 0x3f, npix * (size_t)S * 24, c->stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(acc.p, 0, npix * 48, c->stream)) != hipSuccess) return e;
@@ -3045,14 +3283,14 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
     AccumArgs ma;
     memset(&ma, 0, sizeof ma);
     ma.npix = (int64_t)npix;
-    ma.N = S;  // the general branch
     ma.S = S;
     ma.pass = frame.as<double>();
     ma.acc = acc.as<double>();
+    ma.counts = cnt.as<int64_t>();
     NoiseArgs na;
     memset(&na, 0, sizeof na);
     na.npix = (int64_t)npix;
-    na.n = 2 * S;
+    na.counts = cnt.as<int64_t>();
     na.acc = acc.as<double>();
     na.partial = part.as<double>();
     double *out[3] = {reduce_ms, merge_ms, noise_ms};
@@ -3063,6 +3301,101 @@ int gi_radiance_bench(gi_ctx *c, int aa, int w, int h, int warmup, int reps, dou
         if (k == 0) launch_reduce_radiance(ra, c->stream);
         else if (k == 1) launch_accum_merge(ma, c->stream);
         else launch_accum_noise(na, c->stream);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(e1, c->stream)) != hipSuccess) return e;
+        if ((e = hipEventSynchronize(e1)) != hipSuccess) return e;
+        float t = 0.f;
+        if ((e = hipEventElapsedTime(&t, e0, e1)) != hipSuccess) return e;
+        if (i >= warmup) ms.push_back(t);
+      }
+      std::sort(ms.begin(), ms.end());
+      if (out[k]) *out[k] = ms.size() % 2 ? ms[ms.size() / 2] : 0.5 * (ms[ms.size() / 2 - 1] + ms[ms.size() / 2]);
+    }
+    return hipSuccess;
+  };
+  const hipError_t e = run();
+  (void)hipStreamSynchronize(c->stream);
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  HIPCHK(c, e);
+  return GI_OK;
+}
+
+// Diagnostics: the adaptive passes' kernels on a synthetic frame, as gi_radiance_bench does it.
+// select = tile_error_kernel + tile_select_kernel; the masked fold takes the pixel list of a
+// checkerboard of tiles (half of them active); the whole-frame fold for comparison.
+int gi_adaptive_bench(gi_ctx *c, int w, int h, int tile_px, int warmup, int reps, double *select_ms,
+                      double *masked_merge_ms, double *merge_ms) {
+  if (!c) return GI_ERR_ARG;
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31) || tile_px < 4 || tile_px > 64 ||
+      warmup < 0 || reps < 1 || reps > 10000)
+    return fail(c, GI_ERR_ARG, "adaptive bench: bad size or repetition count");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)w * h;
+  const int tx = (w + tile_px - 1) / tile_px, ty = (h + tile_px - 1) / tile_px;
+  const size_t nt = (size_t)tx * ty;
+  std::vector<int32_t> pix;
+  for (int t = 0; t < tx * ty; t++) {
+    if (((t % tx) + (t / tx)) % 2) continue;
+    const int x0 = (t % tx) * tile_px, y0 = (t / tx) * tile_px;
+    for (int y = y0; y < std::min(h, y0 + tile_px); y++)
+      for (int x = x0; x < std::min(w, x0 + tile_px); x++) {
+        pix.push_back(x);
+        pix.push_back(y);
+      }
+  }
+  TmpBuf pixels, frame, acc, cnt, terr, tmin, tmask;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto run = [&]() -> hipError_t {
+    hipError_t e;
+    if ((e = upload(pixels, pix.data(), pix.size() * 4, c->stream)) != hipSuccess) return e;
+    if ((e = frame.ensure(npix * 48)) != hipSuccess) return e;
+    if ((e = acc.ensure(npix * 48)) != hipSuccess) return e;
+    if ((e = cnt.ensure(npix * 8)) != hipSuccess) return e;
+    if ((e = terr.ensure(nt * 8)) != hipSuccess) return e;
+    if ((e = tmin.ensure(nt * 8)) != hipSuccess) return e;
+    if ((e = tmask.ensure(nt)) != hipSuccess) return e;
+    // bytes 0x3f: every double is 4.7e-4; counts of bytes 0x01: the general branches
+    if ((e = hipMemsetAsync(frame.p, 0x3f, npix * 48, c->stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(acc.p, 0x3f, npix * 48, c->stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(cnt.p, 0x01, npix * 8, c->stream)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&e0)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&e1)) != hipSuccess) return e;
+    TileArgs ta;
+    memset(&ta, 0, sizeof ta);
+    ta.width = w; ta.height = h; ta.T = tile_px; ta.tiles_x = tx; ta.tiles_y = ty;
+    ta.acc = acc.as<double>();
+    ta.counts = cnt.as<int64_t>();
+    ta.tile_error = terr.as<double>();
+    ta.tile_nmin = tmin.as<int64_t>();
+    SelectArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.tiles_x = tx; sa.tiles_y = ty; sa.dilate = 1;
+    sa.min_samples = 8;
+    sa.threshold = 0.02;
+    sa.tile_error = ta.tile_error;
+    sa.tile_nmin = ta.tile_nmin;
+    sa.mask = tmask.as<uint8_t>();
+    AccumArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.S = 4;
+    ma.pass = frame.as<double>();
+    ma.acc = acc.as<double>();
+    ma.counts = cnt.as<int64_t>();
+    ma.width = w;
+    double *out[3] = {select_ms, masked_merge_ms, merge_ms};
+    for (int k = 0; k < 3; k++) {
+      std::vector<float> ms;
+      ma.npix = k == 1 ? (int64_t)pix.size() / 2 : (int64_t)npix;
+      ma.pixels = k == 1 ? pixels.as<int2>() : nullptr;
+      for (int i = 0; i < warmup + reps; i++) {
+        if ((e = hipEventRecord(e0, c->stream)) != hipSuccess) return e;
+        if (k == 0) {
+          launch_tile_error(ta, c->stream);
+          launch_tile_select(sa, c->stream);
+        } else {
+          launch_accum_merge(ma, c->stream);
+        }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = hipEventRecord(e1, c->stream)) != hipSuccess) return e;
         if ((e = hipEventSynchronize(e1)) != hipSuccess) return e;

@@ -20,19 +20,25 @@ struct RadianceArgs {
   double *samples;          // [W * H * S * 3] or null
 };
 
-// accum_merge_kernel: fold the pass frame {m, M2} of S samples into the accumulator {mu, A} of N
+// accum_merge_kernel: fold the pass frame {m, M2} of S samples into the accumulator {mu, A}, each
+// pixel under its own count n_p (counts[p] += S). pixels == null: thread i folds pixel i of the
+// frame; else thread i folds pixel pixels[i] (a masked pass's list) and the others stay as they are
 struct AccumArgs {
-  int64_t npix;
-  int64_t N;                // samples the accumulator holds before this pass
+  int64_t npix;             // pixels to fold: the frame's, or the list's
   int64_t S;
-  const double *pass;       // [npix * 6]
-  double *acc;              // [npix * 6]
+  const double *pass;       // [W * H * 6]
+  double *acc;              // [W * H * 6]
+  int64_t *counts;          // [W * H] samples each pixel holds
+  const int2 *pixels;       // [npix] or null
+  int32_t width;            // frame width (with a list)
 };
 
-// radiance_resolve_kernel: mean = (float)m, variance = (float)(M2 / (n - 1) / n), 0 when n < 2
+// radiance_resolve_kernel: mean = (float)m, variance = (float)(M2 / (n - 1) / n), 0 when n < 2;
+// n = counts[p] when counts is given (the accumulator), else the frame's n (one pass)
 struct ResolveArgs {
   int64_t npix;
   int64_t n;
+  const int64_t *counts;    // [npix] or null
   const double *frame;      // [npix * 6]
   float *mean, *variance;   // [npix * 3] each, either may be null
 };
@@ -42,9 +48,41 @@ struct ResolveArgs {
 constexpr int NOISE_BLOCK = 256;
 struct NoiseArgs {
   int64_t npix;
-  int64_t n;
+  const int64_t *counts;    // [npix] samples per pixel (a pixel below 2 adds 0)
   const double *acc;        // [npix * 6]
   double *partial;          // [ceil(npix / NOISE_BLOCK)]
+};
+
+// count_stats_kernel: smallest count and sum of counts per block of 256 pixels (integers: any
+// order gives the same result); partial = {min, sum} per block
+struct CountArgs {
+  int64_t npix;
+  const int64_t *counts;    // [npix]
+  int64_t *partial;         // [ceil(npix / 256) * 2]
+};
+
+// tile_error_kernel (adaptive passes): one wave per tile of T x T pixels, TILE_WAVES tiles per
+// block. Slot q = y_in_tile * T + x_in_tile holds the pixel's error (accum_noise_kernel's e_p
+// under its own count; 0 outside the image or below two samples); lane l sums the slots
+// q = l, l + 64, ... in that order, then x[l] += x[l + h] for h = 32 .. 1; error = x[0] / pixels
+// of the tile inside the image. nmin = the smallest count of those pixels.
+constexpr int TILE_WAVES = 4;
+struct TileArgs {
+  int32_t width, height, T, tiles_x, tiles_y;
+  const double *acc;        // [W * H * 6]
+  const int64_t *counts;    // [W * H]
+  double *tile_error;       // [tiles]
+  int64_t *tile_nmin;       // [tiles]
+};
+
+// tile_select_kernel: one thread per tile, the selection of gi.h "adaptive passes"
+struct SelectArgs {
+  int32_t tiles_x, tiles_y, dilate;
+  int64_t min_samples, max_samples;
+  double threshold;
+  const double *tile_error;
+  const int64_t *tile_nmin;
+  uint8_t *mask;            // [tiles] 1 = active
 };
 
 // tonemap_kernel: one thread per channel value
@@ -59,6 +97,9 @@ void launch_reduce_radiance(const RadianceArgs &a, hipStream_t st);
 void launch_accum_merge(const AccumArgs &a, hipStream_t st);
 void launch_radiance_resolve(const ResolveArgs &a, hipStream_t st);
 void launch_accum_noise(const NoiseArgs &a, hipStream_t st);
+void launch_count_stats(const CountArgs &a, hipStream_t st);
+void launch_tile_error(const TileArgs &a, hipStream_t st);
+void launch_tile_select(const SelectArgs &a, hipStream_t st);
 void launch_tonemap(const TonemapArgs &a, hipStream_t st);
 
 }  // namespace gi

@@ -9,6 +9,9 @@
 //   accum_merge_kernel       one thread per pixel: a finished pass folded into the accumulator
 //   radiance_resolve_kernel  {m, M2} of n samples -> float mean and variance of the mean
 //   accum_noise_kernel       relative standard error of luminance, block tree sum
+//   count_stats_kernel       smallest and summed per-pixel sample count
+//   tile_error_kernel        adaptive passes: the same error per tile, one wave per tile
+//   tile_select_kernel       ... and the tile mask (thresholds, 8-neighbour dilation)
 //   tonemap_kernel           exposure, extended Reinhard curve, clamp
 #include <hip/hip_runtime.h>
 #include "gi_radiance.h"
@@ -64,16 +67,24 @@ __global__ __launch_bounds__(64) void reduce_radiance_kernel(RadianceArgs a) {
 }
 
 // Chan et al.'s pairwise update of (count, mean, M2); an empty accumulator takes the pass as is
+// (each pixel under its own count: a masked pass leaves the pixels outside its list behind)
 __global__ __launch_bounds__(256) void accum_merge_kernel(AccumArgs a) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.npix) return;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.npix) return;
+  int64_t p = i;
+  if (a.pixels) {
+    const int2 pc = a.pixels[i];
+    p = (int64_t)pc.y * a.width + pc.x;
+  }
   const double *f = a.pass + p * 6;
   double *g = a.acc + p * 6;
-  if (a.N == 0) {
+  const int64_t N = a.counts[p];
+  a.counts[p] = N + a.S;
+  if (N == 0) {
     for (int c = 0; c < 6; c++) g[c] = f[c];
     return;
   }
-  const double S = (double)a.S, N1 = (double)(a.N + a.S), NS = (double)a.N * S;
+  const double S = (double)a.S, N1 = (double)(N + a.S), NS = (double)N * S;
   for (int c = 0; c < 3; c++) {
     const double d = f[c] - g[c];
     g[c] = g[c] + (d * S) / N1;
@@ -85,11 +96,21 @@ __global__ __launch_bounds__(256) void radiance_resolve_kernel(ResolveArgs a) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= a.npix) return;
   const double *f = a.frame + p * 6;
-  const double n = (double)a.n, n1 = (double)(a.n - 1);
+  const int64_t np = a.counts ? a.counts[p] : a.n;
+  const double n = (double)np, n1 = (double)(np - 1);
   for (int c = 0; c < 3; c++) {
     if (a.mean) a.mean[3 * p + c] = (float)f[c];
-    if (a.variance) a.variance[3 * p + c] = a.n < 2 ? 0.0f : (float)(f[3 + c] / n1 / n);
+    if (a.variance) a.variance[3 * p + c] = np < 2 ? 0.0f : (float)(f[3 + c] / n1 / n);
   }
+}
+
+// e_p: relative standard error of luminance of accumulator record f under np >= 2 samples
+__device__ __forceinline__ double pixel_error(const double *f, int64_t np) {
+  const double n = (double)np, n1 = (double)(np - 1);
+  const double Y = 0.2126 * f[0] + 0.7152 * f[1] + 0.0722 * f[2];
+  const double v = (0.2126 * 0.2126) * (f[3] / n1 / n) + (0.7152 * 0.7152) * (f[4] / n1 / n) +
+                   (0.0722 * 0.0722) * (f[5] / n1 / n);
+  return sqrt(v) / (Y + 0.01);
 }
 
 __global__ __launch_bounds__(NOISE_BLOCK) void accum_noise_kernel(NoiseArgs a) {
@@ -97,13 +118,9 @@ __global__ __launch_bounds__(NOISE_BLOCK) void accum_noise_kernel(NoiseArgs a) {
   const int t = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * NOISE_BLOCK + t;
   double e = 0.0;
-  if (p < a.npix && a.n >= 2) {
-    const double *f = a.acc + p * 6;
-    const double n = (double)a.n, n1 = (double)(a.n - 1);
-    const double Y = 0.2126 * f[0] + 0.7152 * f[1] + 0.0722 * f[2];
-    const double v = (0.2126 * 0.2126) * (f[3] / n1 / n) + (0.7152 * 0.7152) * (f[4] / n1 / n) +
-                     (0.0722 * 0.0722) * (f[5] / n1 / n);
-    e = sqrt(v) / (Y + 0.01);
+  if (p < a.npix) {
+    const int64_t np = a.counts[p];
+    if (np >= 2) e = pixel_error(a.acc + p * 6, np);
   }
   x[t] = e;
   __syncthreads();
@@ -112,6 +129,79 @@ __global__ __launch_bounds__(NOISE_BLOCK) void accum_noise_kernel(NoiseArgs a) {
     __syncthreads();
   }
   if (t == 0) a.partial[blockIdx.x] = x[0];
+}
+
+__global__ __launch_bounds__(256) void count_stats_kernel(CountArgs a) {
+  __shared__ int64_t mn[256], sm[256];
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * 256 + t;
+  mn[t] = p < a.npix ? a.counts[p] : INT64_MAX;
+  sm[t] = p < a.npix ? a.counts[p] : 0;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if (t < h) {
+      mn[t] = mn[t + h] < mn[t] ? mn[t + h] : mn[t];
+      sm[t] += sm[t + h];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    a.partial[2 * blockIdx.x] = mn[0];
+    a.partial[2 * blockIdx.x + 1] = sm[0];
+  }
+}
+
+// One wave per tile. Consecutive lanes take consecutive slots, so they run along the tile's rows
+// (at T = 8 a tile row is one 384-B run of accumulator records). The lane sums and the wave tree
+// are in the order gi_radiance.h states: lane l's x[l + h] comes from lane l + h by a shuffle, and
+// only the lanes l < h of a step are read afterwards (the others add a value nobody uses).
+__global__ __launch_bounds__(64 * TILE_WAVES) void tile_error_kernel(TileArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6);
+  if (t >= (int64_t)a.tiles_x * a.tiles_y) return;  // the whole wave
+  const int x0 = (int)(t % a.tiles_x) * a.T, y0 = (int)(t / a.tiles_x) * a.T;
+  const int nx = min(a.T, a.width - x0), ny = min(a.T, a.height - y0);
+  double x = 0.0;
+  int64_t nmin = INT64_MAX;
+  for (int q = lane; q < a.T * a.T; q += 64) {
+    const int yy = q / a.T, xx = q - yy * a.T;
+    double e = 0.0;
+    if (xx < nx && yy < ny) {
+      const int64_t p = (int64_t)(y0 + yy) * a.width + (x0 + xx);
+      const int64_t np = a.counts[p];
+      nmin = np < nmin ? np : nmin;
+      if (np >= 2) e = pixel_error(a.acc + p * 6, np);
+    }
+    x += e;
+  }
+  for (int h = 32; h >= 1; h >>= 1) {
+    x += __shfl_down(x, h, 64);
+    const int64_t o = __shfl_down((long long)nmin, h, 64);
+    nmin = o < nmin ? o : nmin;
+  }
+  if (lane == 0) {
+    a.tile_error[t] = x / (double)(nx * ny);
+    a.tile_nmin[t] = nmin;
+  }
+}
+
+__global__ __launch_bounds__(256) void tile_select_kernel(SelectArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)a.tiles_x * a.tiles_y) return;
+  const int tx = (int)(t % a.tiles_x), ty = (int)(t / a.tiles_x);
+  const bool below_max = a.max_samples == 0 || a.tile_nmin[t] < a.max_samples;
+  bool active = a.tile_nmin[t] < a.min_samples || (a.tile_error[t] > a.threshold && below_max);
+  if (!active && a.dilate && below_max) {
+    for (int dy = -1; dy <= 1; dy++)
+      for (int dx = -1; dx <= 1; dx++) {
+        const int ux = tx + dx, uy = ty + dy;
+        if ((dx == 0 && dy == 0) || ux < 0 || uy < 0 || ux >= a.tiles_x || uy >= a.tiles_y) continue;
+        const int64_t u = (int64_t)uy * a.tiles_x + ux;
+        if (a.tile_error[u] > a.threshold && (a.max_samples == 0 || a.tile_nmin[u] < a.max_samples))
+          active = true;
+      }
+  }
+  a.mask[t] = active ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void tonemap_kernel(TonemapArgs a) {
@@ -135,6 +225,17 @@ void launch_radiance_resolve(const ResolveArgs &a, hipStream_t st) {
 }
 void launch_accum_noise(const NoiseArgs &a, hipStream_t st) {
   if (a.npix > 0) accum_noise_kernel<<<nblk(a.npix, NOISE_BLOCK), NOISE_BLOCK, 0, st>>>(a);
+}
+void launch_count_stats(const CountArgs &a, hipStream_t st) {
+  if (a.npix > 0) count_stats_kernel<<<nblk(a.npix, 256), 256, 0, st>>>(a);
+}
+void launch_tile_error(const TileArgs &a, hipStream_t st) {
+  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y;
+  if (nt > 0) tile_error_kernel<<<nblk(nt, TILE_WAVES), 64 * TILE_WAVES, 0, st>>>(a);
+}
+void launch_tile_select(const SelectArgs &a, hipStream_t st) {
+  const int64_t nt = (int64_t)a.tiles_x * a.tiles_y;
+  if (nt > 0) tile_select_kernel<<<nblk(nt, 256), 256, 0, st>>>(a);
 }
 void launch_tonemap(const TonemapArgs &a, hipStream_t st) {
   if (a.nval > 0) tonemap_kernel<<<nblk(a.nval, 256), 256, 0, st>>>(a);

@@ -10,6 +10,8 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
   materials / camera_features / ray_features / denoise: per-pixel feature planes and the
                    edge-avoiding denoise pass (no reference counterpart; gi.h "feature planes
                    and denoise pass")
+  accum_select / accum_add_tiles / accum_add_adaptive / accum_get_counts: adaptive passes over
+                   the noisy tiles of the accumulator (gi.h "adaptive passes")
   render_radiance / render_rays_radiance / accum_* / tonemap / write_image_float: unclamped
                    radiance frames with their variance, accumulation over passes and the tone
                    map (no reference counterpart; gi.h "radiance frames, accumulation over
@@ -44,6 +46,8 @@ EXPORTED = [
     "gi_denoise",
     "gi_render_radiance", "gi_render_rays_radiance", "gi_accum_reset", "gi_accum_add_image",
     "gi_accum_add_rays", "gi_accum_get", "gi_tonemap", "gi_radiance_bench",
+    "gi_accum_get_counts", "gi_adaptive_params_default", "gi_accum_select", "gi_accum_add_tiles",
+    "gi_accum_add_adaptive", "gi_adaptive_bench",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
@@ -96,6 +100,12 @@ class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32),
                 ("sigma_color", C.c_double), ("sigma_depth", C.c_double),
                 ("sigma_albedo", C.c_double)]
+
+
+class AdaptiveParams(C.Structure):
+    """gi_adaptive_params"""
+    _fields_ = [("tile_px", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
+                ("dilate", C.c_int32), ("threshold", C.c_double)]
 
 
 GI_MAX_DEVICES = 64
@@ -211,6 +221,17 @@ def lib():
                                         P(RenderStats)]
         L.gi_accum_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64),
                                    P(C.c_double)]
+        L.gi_accum_get_counts.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64)]
+        L.gi_adaptive_params_default.argtypes = [P(AdaptiveParams)]
+        L.gi_adaptive_params_default.restype = None
+        L.gi_accum_select.argtypes = [C.c_void_p, P(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                      P(C.c_int64), P(C.c_int64)]
+        L.gi_accum_add_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, P(C.c_int64),
+                                         P(RenderStats)]
+        L.gi_accum_add_adaptive.argtypes = [C.c_void_p, C.c_int, P(AdaptiveParams), C.c_void_p,
+                                            P(C.c_int64), P(RenderStats)]
+        L.gi_adaptive_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        P(C.c_double), P(C.c_double), P(C.c_double)]
         L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                  C.c_double, C.c_void_p, C.c_void_p]
         L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -243,6 +264,17 @@ def default_params():
 def default_denoise_params():
     p = DenoiseParams()
     lib().gi_denoise_params_default(C.byref(p))
+    return p
+
+
+def adaptive_params(**kw):
+    """gi_adaptive_params: the defaults (gi_adaptive_params_default) with the given fields set."""
+    p = AdaptiveParams()
+    lib().gi_adaptive_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(AdaptiveParams._fields_):
+            raise TypeError(f"unknown adaptive parameter {k}")
+        setattr(p, k, v)
     return p
 
 
@@ -539,6 +571,67 @@ class Renderer:
                                        var.ctypes.data if w else None, C.byref(n),
                                        C.byref(noise)))
         return mean, var, n.value, noise.value
+
+    def accum_get_counts(self):
+        """(per-pixel sample counts [H, W] int64, their sum) of the accumulator
+        (gi_accum_get_counts)."""
+        w, h = getattr(self, "_accum_size", (0, 0))
+        counts = np.zeros((h, w), dtype=np.int64)
+        total = C.c_int64(0)
+        self._check(lib().gi_accum_get_counts(self._ctx, counts.ctypes.data if w else None,
+                                              C.byref(total)))
+        return counts, total.value
+
+    def _tiles(self, tile_px):
+        w, h = getattr(self, "_accum_size", (0, 0))
+        t = max(1, int(tile_px))
+        return ((w + t - 1) // t) * ((h + t - 1) // t)
+
+    def accum_select(self, params=None, **kw):
+        """The tiles an adaptive pass would refine (gi_accum_select): (mask [tiles] uint8,
+        tile_error [tiles] float64, active tiles, active pixels). params: AdaptiveParams, or the
+        defaults with the keyword fields set."""
+        p = params if params is not None else adaptive_params(**kw)
+        nt = self._tiles(p.tile_px)
+        mask = np.zeros(nt, dtype=np.uint8)
+        err = np.zeros(nt, dtype=np.float64)
+        at, ap = C.c_int64(0), C.c_int64(0)
+        self._check(lib().gi_accum_select(self._ctx, C.byref(p), mask.ctypes.data,
+                                          err.ctypes.data, C.byref(at), C.byref(ap)))
+        return mask, err, at.value, ap.value
+
+    def accum_add_tiles(self, aa, tile_px, mask):
+        """One camera pass over the tiles with mask != 0, folded into their pixels only
+        (gi_accum_add_tiles). Returns (active pixels, stats)."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).ravel()
+        if 4 <= tile_px <= 64 and getattr(self, "_accum_size", None) \
+                and mask.size != self._tiles(tile_px):
+            raise ValueError(f"{self._tiles(tile_px)} tiles expected, got {mask.size}")
+        st = RenderStats()
+        ap = C.c_int64(0)
+        self._check(lib().gi_accum_add_tiles(self._ctx, aa, tile_px, mask.ctypes.data,
+                                             C.byref(ap), C.byref(st)))
+        return ap.value, _stats_dict(st)
+
+    def accum_add_adaptive(self, aa, params=None, **kw):
+        """Select and refine in one call (gi_accum_add_adaptive). Returns (mask [tiles] uint8,
+        active pixels, stats)."""
+        p = params if params is not None else adaptive_params(**kw)
+        mask = np.zeros(self._tiles(p.tile_px), dtype=np.uint8)
+        st = RenderStats()
+        ap = C.c_int64(0)
+        self._check(lib().gi_accum_add_adaptive(self._ctx, aa, C.byref(p), mask.ctypes.data,
+                                                C.byref(ap), C.byref(st)))
+        return mask, ap.value, _stats_dict(st)
+
+    def adaptive_bench(self, width, height, tile_px=8, warmup=5, reps=50):
+        """Median HIP-event ms of the tile selection, the masked fold at half the tiles and the
+        whole-frame fold on a synthetic frame (diagnostics; gi_adaptive_bench)."""
+        t = [C.c_double(0.0) for _ in range(3)]
+        self._check(lib().gi_adaptive_bench(self._ctx, width, height, tile_px, warmup, reps,
+                                            C.byref(t[0]), C.byref(t[1]), C.byref(t[2])))
+        return {"select_ms": t[0].value, "masked_merge_ms": t[1].value,
+                "accum_merge_ms": t[2].value}
 
     def tonemap(self, radiance, exposure=1.0, white=0.0, want_float=False):
         """Exposure, extended Reinhard curve (white > 0; 0: linear) and clamp of a radiance frame

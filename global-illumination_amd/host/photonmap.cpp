@@ -13,6 +13,9 @@
 // accumulator (gi_accum_*), after each pass -noise stops at noise <= T (default passes: 1, or
 // 4096 under -noise), the written image is gi_tonemap of the unclamped mean (E default 1, W
 // default 0: linear) and FILE (.pfm / .hdr) receives that mean. One device only.
+// Extension: -adaptive [TILE] (TILE 4..64, default 8), only together with -noise T: whole-frame
+// passes until every pixel has the default min_samples, then gi_accum_add_adaptive passes with
+// threshold T over TILE x TILE tiles, until no tile is active or -passes is used up.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -99,9 +102,32 @@ static bool ParseNumber(const char *text, double *v) {
   return end != text && !*end && *v == *v && *v - *v == 0.0;  // a finite number, nothing after it
 }
 
-// -passes / -noise / -exposure / -white / -radiance
+// Takes `-adaptive [TILE]` out of argv: the token after it is TILE when it is an integer (false
+// when that is outside 4..64). The last -adaptive wins.
+static bool TakeAdaptive(int &argc, char **argv, int &tile) {
+  for (int a = 1; a < argc;) {
+    if (strcmp(argv[a], "-adaptive")) { a++; continue; }
+    int take = 1;
+    tile = 8;
+    if (a + 1 < argc) {
+      char *end = nullptr;
+      const long v = strtol(argv[a + 1], &end, 10);
+      if (end != argv[a + 1] && !*end) {
+        if (v < 4 || v > 64) return false;
+        tile = (int)v;
+        take = 2;
+      }
+    }
+    for (int k = a + take; k < argc; k++) argv[k - take] = argv[k];
+    argc -= take;
+  }
+  return true;
+}
+
+// -passes / -noise / -exposure / -white / -radiance / -adaptive
 struct RadianceFlags {
   bool any = false, have_noise = false;
+  int adaptive_tile = 0;  // 0: uniform passes
   int passes = 0;  // 0: not given
   double noise = 0.0, exposure = 1.0, white = 0.0;
   const char *file = nullptr;
@@ -110,6 +136,7 @@ struct RadianceFlags {
 static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
   const char *t = nullptr;
   double v = 0.0;
+  if (!TakeAdaptive(argc, argv, r.adaptive_tile)) return "-adaptive";
   if (!TakeValue(argc, argv, "-passes", &t)) return "-passes";
   if (t) {
     char *end = nullptr;
@@ -147,6 +174,7 @@ static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
     r.file = t;
     r.any = true;
   }
+  if (r.adaptive_tile && !r.have_noise) return "-adaptive";
   if (r.passes == 0) r.passes = r.have_noise ? 4096 : 1;
   return nullptr;
 }
@@ -261,19 +289,31 @@ int main(int argc, char **argv) {
   std::vector<float> rgbf(denoise_levels || rad.any ? (size_t)w * h * 3 : 0);
   std::vector<float> mean(rad.any ? (size_t)w * h * 3 : 0);
   int passes_done = 0;
-  long long acc_n = 0;
+  long long acc_n = 0, acc_total = 0, acc_max = 0;
   double acc_noise = 0.0;
   if (rad.any) {
     // passes under seed, seed + 1, ... from the same maps, folded into the accumulator; the
     // written image is the tone-mapped unclamped mean
     memset(&rs, 0, sizeof rs);
     bool ok = gi_accum_reset(ctx, w, h) == GI_OK;
+    gi_adaptive_params ap;
+    gi_adaptive_params_default(&ap);
+    ap.tile_px = rad.adaptive_tile ? rad.adaptive_tile : ap.tile_px;
+    ap.threshold = rad.noise;
+    int64_t least = 0;  // the smallest per-pixel count so far
     for (int i = 0; ok && i < rad.passes; i++) {
       gi_params Pi = P;
       Pi.seed = P.seed + (uint64_t)i;
       gi_render_stats ps;
       prog.last[0] = -1;
-      ok = gi_set_params(ctx, &Pi) == GI_OK && gi_accum_add_image(ctx, aa, &ps) == GI_OK;
+      ok = gi_set_params(ctx, &Pi) == GI_OK;
+      if (ok && rad.adaptive_tile && least >= ap.min_samples) {
+        int64_t active = 0;
+        ok = gi_accum_add_adaptive(ctx, aa, &ap, nullptr, &active, &ps) == GI_OK;
+        if (ok && active == 0) break;  // every tile is at the threshold: nothing was rendered
+      } else if (ok) {
+        ok = gi_accum_add_image(ctx, aa, &ps) == GI_OK;
+      }
       if (!ok) break;
       passes_done++;
       rs.render_s += ps.render_s;
@@ -281,11 +321,20 @@ int main(int argc, char **argv) {
       rs.monte_carlo_rays += ps.monte_carlo_rays; rs.transmissive_samples += ps.transmissive_samples;
       rs.specular_samples += ps.specular_samples; rs.indirect_samples += ps.indirect_samples;
       rs.caustic_samples += ps.caustic_samples;
-      if (rad.have_noise) {  // defined from two samples per pixel on
+      if (rad.adaptive_tile) {
+        ok = gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
+      } else if (rad.have_noise) {  // defined from two samples per pixel on
         int64_t n = 0;
         ok = gi_accum_get(ctx, nullptr, nullptr, &n, &acc_noise) == GI_OK;
         if (ok && n >= 2 && acc_noise <= rad.noise) break;
       }
+    }
+    if (ok && rad.adaptive_tile) {
+      std::vector<int64_t> counts((size_t)w * h);
+      int64_t total = 0;
+      ok = gi_accum_get_counts(ctx, counts.data(), &total) == GI_OK;
+      acc_total = total;
+      for (int64_t v : counts) acc_max = v > acc_max ? v : acc_max;
     }
     int64_t n = 0;
     ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK &&
@@ -330,7 +379,10 @@ int main(int argc, char **argv) {
     if (P.indirect_illum) { printf("  # Indirect Samples = %llu\n", (unsigned long long)rs.indirect_samples); total += rs.indirect_samples; }
     if (P.caustic_illum) { printf("  # Caustic Samples = %llu\n", (unsigned long long)rs.caustic_samples); total += rs.caustic_samples; }
     printf("Total Rays: %llu\n", total);
-    if (rad.any)
+    if (rad.adaptive_tile)
+      printf("Accumulated image: %d passes, %lld samples, %lld to %lld per pixel, noise = %.6g\n",
+             passes_done, acc_total, acc_n, acc_max, acc_noise);
+    else if (rad.any)
       printf("Accumulated image: %d passes, N = %lld samples per pixel, noise = %.6g\n", passes_done,
              acc_n, acc_noise);
     if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);

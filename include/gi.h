@@ -356,26 +356,80 @@ int gi_render_rays_radiance(gi_ctx *ctx, int width, int height, int spp, const g
                             const uint64_t *ids /* may be NULL */, float *mean, float *variance,
                             double *samples, gi_render_stats *stats);
 /* Accumulator, on the device, one per context: per pixel and channel a running fp64 mean mu and
- * sum of squared deviations A, and one sample count N for the frame. gi_accum_reset sizes and
- * empties it (N = 0). gi_accum_add_image / gi_accum_add_rays render one pass of the reset's
- * width x height under the context's current parameters and fold its (S, m, M2) in, once, after
- * the render has completed; the first pass is taken as is, later ones by
+ * sum of squared deviations A, and per pixel one int64 sample count N (written n_p where pixels
+ * differ). gi_accum_reset sizes and empties it (every N = 0). gi_accum_add_image /
+ * gi_accum_add_rays render one pass of the reset's width x height under the context's current
+ * parameters and fold its (S, m, M2) into every pixel, once, after the render has completed; a
+ * pixel with N = 0 takes the pass as is, the others by
  *   d = m - mu,  N' = N + S,  mu' = mu + (d * S) / N',  A' = (A + M2) + ((d * d) * (N * S)) / N'.
+ * (N, S and N' are converted to double once each; N * S is the product of the two doubles.)
  * The caller decorrelates the passes: for camera passes change `seed` with gi_set_params between
  * them (gi_set_params keeps the photon maps, their kd trees and the -cache irradiance: a second
  * render under another seed is an independent estimate from the same maps); for ray passes give
- * other ids. gi_accum_get (every output optional): mean = (float)mu, variance =
- * (float)(A / (N - 1) / N) (0 when N < 2), *nsamples = N, *noise = the mean over the pixels of
- * sqrt(v) / (Y + 0.01) with Y = 0.2126 mu_r + 0.7152 mu_g + 0.0722 mu_b and v = 0.2126^2 v_r +
- * 0.7152^2 v_g + 0.0722^2 v_b (v_c the unrounded A / (N - 1) / N): the relative standard error
- * of luminance, summed in a fixed order (blocks of 256 pixels by a tree, then block by block),
- * so the same accumulator always reports the same bits; 0 when N < 2. GI_ERR_STATE before a
- * reset; a pass always has the reset's size (a ray pass takes width * height * spp rays). */
+ * other ids. gi_accum_get (every output optional), each pixel under its own N: mean =
+ * (float)mu, variance = (float)(A / (N - 1) / N) (0 where N < 2), *nsamples = the smallest N of
+ * the frame (every pixel's N while only whole-frame passes were added), *noise = the mean over
+ * the pixels of e = sqrt(v) / (Y + 0.01) with Y = 0.2126 mu_r + 0.7152 mu_g + 0.0722 mu_b and v =
+ * 0.2126^2 v_r + 0.7152^2 v_g + 0.0722^2 v_b (v_c the unrounded A / (N - 1) / N): the relative
+ * standard error of luminance (e = 0 where N < 2), summed in a fixed order (blocks of 256 pixels
+ * by a tree, then block by block), so the same accumulator always reports the same bits.
+ * GI_ERR_STATE before a reset; a pass always has the reset's size (a ray pass takes width *
+ * height * spp rays). */
 int gi_accum_reset(gi_ctx *ctx, int width, int height);
 int gi_accum_add_image(gi_ctx *ctx, int aa, gi_render_stats *stats);
 int gi_accum_add_rays(gi_ctx *ctx, int spp, const gi_ray *rays, const uint64_t *ids,
                       gi_render_stats *stats);
 int gi_accum_get(gi_ctx *ctx, float *mean, float *variance, int64_t *nsamples, double *noise);
+/* counts: W*H int64, rows from the bottom (optional); *total = sum of n_p (optional) */
+int gi_accum_get_counts(gi_ctx *ctx, int64_t *counts, int64_t *total);
+
+/* ---- adaptive passes: refine only the noisy tiles of the accumulator --------------------- */
+/* The accumulator's frame is cut into tiles of tile_px x tile_px pixels: tiles_x = ceil(W /
+ * tile_px), tiles_y likewise, tile t = ty * tiles_x + tx with ty = 0 at the bottom; the tiles of
+ * the last column and row are clipped by the frame. No reference counterpart. One device only:
+ * GI_ERR_UNSUPPORTED on a device set, GI_ERR_STATE before gi_accum_reset.
+ *
+ * Tile error. A tile has T * T slots (T = tile_px), slot q = y_in_tile * T + x_in_tile. A slot
+ * inside the frame holds its pixel's e as gi_accum_get defines it under the pixel's own n_p (0
+ * where n_p < 2); a slot outside holds 0. In fp64: x[l] (l = 0 .. 63) = the sum of the slots
+ * q = l, l + 64, ... in ascending q, starting from 0; then x[l] += x[l + h] for l < h, for h = 32,
+ * 16, .., 1; tile_error = x[0] / (pixels of the tile inside the frame). n_min = the smallest n_p
+ * of those pixels.
+ * Selection. below_max = (max_samples == 0 or n_min < max_samples); by_error = (tile_error >
+ * threshold and below_max); core = (n_min < min_samples or by_error); dilated = (dilate and not
+ * core and below_max and one of the tile's up to 8 neighbours is by_error); active = core or
+ * dilated. */
+typedef struct gi_adaptive_params {
+  int32_t tile_px;      /* 4..64, default 8 */
+  int32_t min_samples;  /* >= 0: a tile whose smallest n_p is below this is always active; default 8 */
+  int32_t max_samples;  /* 0 = none; a tile whose smallest n_p is >= this is never active by its error */
+  int32_t dilate;       /* 0 or 1, default 1 */
+  double threshold;     /* finite, >= 0; default 0.02 */
+} gi_adaptive_params;
+void gi_adaptive_params_default(gi_adaptive_params *p);
+/* The selection of the accumulator as it stands. mask (optional): one byte per tile, 1 = active;
+ * tile_error (optional): one double per tile; *active_tiles, *active_pixels (optional): the
+ * active tiles and the pixels inside the frame they hold. GI_ERR_ARG for a null p, tile_px
+ * outside 4..64, a negative min_samples or max_samples, dilate not 0 or 1, or a threshold that
+ * is negative or not finite. Needs no scene. */
+int gi_accum_select(gi_ctx *ctx, const gi_adaptive_params *p, uint8_t *mask /* tiles, optional */,
+                    double *tile_error /* tiles, optional */, int64_t *active_tiles,
+                    int64_t *active_pixels);
+/* One camera pass (as gi_accum_add_image: current parameters, -dof lens samples) over the pixels
+ * of the tiles with mask[t] != 0, in tile order and row-major inside a tile, folded into those
+ * pixels only, once, after the render has completed; every other pixel keeps mu, A and n_p bit
+ * for bit. A sample's RNG stream is keyed by its place in the frame, not in the pass, so a pixel
+ * gets the samples a whole-frame pass under the same seed gives it. The counters are those of
+ * the pixels rendered (screen_rays: those of their *active_pixels * 4^aa * dof_test primary rays
+ * that hit the scene, as in every render). An empty mask returns
+ * GI_OK with *active_pixels = 0 and zeroed stats and launches nothing. GI_ERR_ARG for tile_px
+ * outside 4..64, a null mask or aa outside 0..15. */
+int gi_accum_add_tiles(gi_ctx *ctx, int aa, int tile_px, const uint8_t *mask,
+                       int64_t *active_pixels, gi_render_stats *stats);
+/* gi_accum_select + gi_accum_add_tiles under the same parameters; mask (optional) receives the
+ * selection. Errors as those two. */
+int gi_accum_add_adaptive(gi_ctx *ctx, int aa, const gi_adaptive_params *p, uint8_t *mask,
+                          int64_t *active_pixels, gi_render_stats *stats);
 /* Tone map of a radiance frame (W*H*3 floats), per channel in fp64: x = exposure * c;
  * y = x * (1 + x / (white * white)) / (1 + x) when white > 0 (extended Reinhard: `white` maps to
  * 1), y = x when white == 0; clamped to [0, 1], rounded to float32. Linear output, as the
@@ -406,6 +460,12 @@ int gi_knn_bench(gi_ctx *ctx, int map, int64_t n, const double *points, const do
  * only a context; leaves its accumulator alone. No reference counterpart (measurement only). */
 int gi_radiance_bench(gi_ctx *ctx, int aa, int width, int height, int warmup, int reps,
                       double *reduce_ms, double *merge_ms, double *noise_ms);
+/* Diagnostics: the adaptive passes' kernels on a synthetic width x height frame, timed as in
+ * gi_radiance_bench (outputs optional): the tile error and selection kernels together, the fold
+ * of a masked pass over a checkerboard of tiles (half of them active) and the whole-frame fold.
+ * Needs only a context; leaves its accumulator alone. No reference counterpart. */
+int gi_adaptive_bench(gi_ctx *ctx, int width, int height, int tile_px, int warmup, int reps,
+                      double *select_ms, double *masked_merge_ms, double *merge_ms);
 int gi_intersect_batch(gi_ctx *ctx, int64_t n, const double *org, const double *dir,
                        int32_t *hit, double *t, double *point, double *normal, int32_t *material);
 /* Test seam: the device's fp64 math on host inputs, fn = 0 acos(x), 1 sin(x), 2 cos(x),
