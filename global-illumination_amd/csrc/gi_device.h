@@ -33,11 +33,17 @@ GI_HD uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
   return z ^ (z >> 31);
 }
-GI_HD uint64_t stream_key(uint64_t seed, uint64_t kind, uint64_t a, uint64_t b) {
+// A stream's key in two steps: the prefix takes (seed, kind, a) and the finish b, so that the
+// streams (a, 0), (a, 1), ... of one a (a primary sample's indirect paths) share one prefix.
+GI_HD uint64_t stream_key_prefix(uint64_t seed, uint64_t kind, uint64_t a) {
   uint64_t k = mix64(seed ^ (kind * 0xA0761D6478BD642FULL));
-  k = mix64(k + a * 0xE7037ED1A0B428DBULL + 0x8EBC6AF09C88C6E3ULL);
-  k = mix64(k + b * 0x589965CC75374CC3ULL + 0x1D8E4E27C47D124FULL);
-  return k;
+  return mix64(k + a * 0xE7037ED1A0B428DBULL + 0x8EBC6AF09C88C6E3ULL);
+}
+GI_HD uint64_t stream_key_finish(uint64_t prefix, uint64_t b) {
+  return mix64(prefix + b * 0x589965CC75374CC3ULL + 0x1D8E4E27C47D124FULL);
+}
+GI_HD uint64_t stream_key(uint64_t seed, uint64_t kind, uint64_t a, uint64_t b) {
+  return stream_key_finish(stream_key_prefix(seed, kind, a), b);
 }
 enum { KIND_PRIMARY = 1, KIND_TRANS = 2, KIND_SPEC = 3, KIND_IND = 4,
        KIND_PHOTON_GLOBAL = 5, KIND_PHOTON_CAUSTIC = 6 };
@@ -696,18 +702,28 @@ GI_HD V rotate(V v, V axis, double theta) {  // R3Vector::Rotate, R3Vector.cpp:3
   v = v - cr * st;
   return v;
 }
-GI_HD V diffuse_sample(V n, double ct, Rng &rng) {  // Diffuse_ImportanceSample :162-185
+// Diffuse_ImportanceSample :162-185 in two steps. The tangent depends on the surface alone
+// (normal, side), the sample on the two draws: a caller that samples one surface many times
+// (the indirect paths of a primary hit) computes the tangent once.
+GI_HD V diffuse_tangent(V n, double ct) {  // n as stored; flipped to the viewer's side here
   if (ct < 0) n = -n;
-  double theta = gm::acos(sqrt(rng.next()));
-  double phi = 2 * kPi * rng.next();
   V perp = mk(n.y, -n.x, 0);
   if (1.0 - fabs(n.z) < 0.1) perp = mk(n.z, 0, -n.x);
-  perp = normalize(perp);
+  return normalize(perp);
+}
+GI_HD V diffuse_sample_t(V n, V perp, Rng &rng) {  // n already on the viewer's side
+  double theta = gm::acos(sqrt(rng.next()));
+  double phi = 2 * kPi * rng.next();
   double st, ctt;
   gm::sincos(theta, st, ctt);
   V r = perp * st + n * ctt;
   r = rotate(r, n, phi);
   return normalize(r);
+}
+GI_HD V diffuse_sample(V n, double ct, Rng &rng) {
+  V perp = diffuse_tangent(n, ct);
+  if (ct < 0) n = -n;
+  return diffuse_sample_t(n, perp, rng);
 }
 GI_HD V specular_sample(V ex, double nsh, double ct, Rng &rng) {  // :189-216
   double lim = (1.0 - gm::acos(fabs(ct)) * 2.0 / kPi);

@@ -31,7 +31,13 @@ struct Spawn {
   int32_t q_glob, q_caus; // primary-hit photon-map queries (photon_viz / caustic)
   int32_t tri;            // triangle hit (gi_device.h Hit::tri): the sample paths leave from it
   double wt[3];           // indirect paths' outer weight kd / n_i (raytracer.cpp:112-135)
+  // what every indirect path of the sample shares, computed once by primary_shade (valid when
+  // hit && n_i > 0): the RNG stream key before its last round (stream_key_prefix of the sample's
+  // stream id) and diffuse_sample's tangent of (n, ct)
+  uint64_t ind_key;
+  double perp[3];
 };
+static_assert(sizeof(Spawn) == 200, "spawn record is 200 bytes");
 
 // shading half of a photon-map query (search half is float4 {x, y, z, meta})
 // an indirect sample path whose first bounce hit a material with a specular or transmissive

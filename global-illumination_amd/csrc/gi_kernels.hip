@@ -122,10 +122,10 @@ __device__ __forceinline__ void camera_ray(const DCamera &cam, int dof, int i, i
 
 // RayTrace (raytracer.cpp:174-233) of one primary ray up to the sample fan-outs: intersection,
 // ambient + direct light, fan counts; writes sample b's spawn record, which the path kernels
-// expand. `eye` is the view point the hit is shaded from.
+// expand. `eye` is the view point the hit is shaded from, `psample` the sample's stream id.
 __device__ __forceinline__ void primary_shade(const RenderArgs &a, int64_t b, V org, V dir, V eye,
-                                              Rng &rng, uint64_t &c_ray, uint64_t &c_shadow,
-                                              uint64_t &c_ind) {
+                                              uint64_t psample, Rng &rng, uint64_t &c_ray,
+                                              uint64_t &c_shadow, uint64_t &c_ind) {
   const SceneView &S = a.S;
   const Flags &F = a.F;
   Spawn sp;
@@ -179,6 +179,13 @@ __device__ __forceinline__ void primary_shade(const RenderArgs &a, int64_t b, V 
     sp.mat = h.mat;
     sp.tri = h.tri;
     sp.base[0] = color.r; sp.base[1] = color.g; sp.base[2] = color.b;
+    if (sp.n_i > 0) {
+      // the indirect paths' shared part (ind_kernel), last so that nothing of it stays live
+      // through the shading above
+      sp.ind_key = stream_key_prefix(F.seed, KIND_IND, psample);
+      const V perp = diffuse_tangent(h.n, ct);
+      sp.perp[0] = perp.x; sp.perp[1] = perp.y; sp.perp[2] = perp.z;
+    }
   }
   a.spawn[b] = sp;
   a.npaths[b] = 1u + (uint32_t)(sp.n_t + sp.n_s);
@@ -206,7 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRIMARY_WPE
     rng.init(a.F.seed, KIND_PRIMARY, psample, 0);
     V eye, org, dir;
     camera_ray(a.S.cam, a.F.dof, i, j, a.W, a.H, rng, eye, org, dir);
-    primary_shade(a, b, org, dir, eye, rng, c_ray, c_shadow, c_ind);
+    primary_shade(a, b, org, dir, eye, psample, rng, c_ray, c_shadow, c_ind);
   }
   wave_add(&a.stats[ST_RAY], c_ray);
   wave_add(&a.stats[ST_SHADOW], c_shadow);
@@ -328,8 +335,10 @@ __device__ __forceinline__ void global_query(PathCtx &P, V p, V n, V ex, double 
 // org is also the loop's ray_start). Returns true when the path continues with the bounced ray
 // in (org, dir). DIFFUSE_ONLY: the material has no specular/transmissive term (kt = ks = 0,
 // opaque): R = pt = ps = 0 exactly, so only the query/absorb outcomes remain and the branches
-// with pow/acos/asin/tan are not compiled in.
-template <bool DIFFUSE_ONLY>
+// with pow/acos/asin/tan are not compiled in. UNIT_TW: the caller's tw is exactly (1, 1, 1) (a
+// path's first hit), so the query weight kd * tw / pd is the material's kd_pd table entry, the
+// same bits without the three divisions.
+template <bool DIFFUSE_ONLY, bool UNIT_TW = false>
 __device__ __forceinline__ bool ind_shade(PathCtx &P, const Hit &h, V &org, V &dir, Rng &rng, C3 W,
                                           C3 &tw) {
   const SceneView &S = *P.S;
@@ -348,7 +357,7 @@ __device__ __forceinline__ bool ind_shade(PathCtx &P, const Hit &h, V &org, V &d
   if (ptot > 1.0) rnd *= ptot;
   if (rnd < pd) {
     V ex = reflective_bounce(h.n, view, ct);
-    global_query(P, h.p, h.n, ex, ct, h.mat, W * (ldc(m.kd) * tw / pd));
+    global_query(P, h.p, h.n, ex, ct, h.mat, W * (UNIT_TW ? ldc(m.kd_pd) : ldc(m.kd) * tw / pd));
     return false;
   }
   if (DIFFUSE_ONLY) return false;
@@ -720,17 +729,27 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
     int pslot = 1 + sp.n_t + sp.n_s + s;
     const int64_t tau = t;
     int64_t g = a.ind_g0 + tau;
-    int pix, i, j, k;
-    uint64_t psample;
-    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
     PathCtx P;
     path_init(P, a, g, pb, pslot);
     P.fixed[0] = a.qind_base + tau;  // at most one (global) query per indirect path
     P.hint = sp.tri;
     Rng rng;
-    rng.init(a.F.seed, KIND_IND, psample, (uint64_t)s);
     V p = ld3(sp.p), n = ld3(sp.n);
-    V sb = (a.dbg >= 2) ? n : diffuse_sample(n, sp.ct, rng);
+    V sb;
+    if (SPLIT) {
+      // what the primary's samples share comes from its spawn record (primary_shade): the
+      // stream key up to its last round, which takes s (wave-uniform: scalar work), and the
+      // sampler's tangent. The same operations as rng.init / diffuse_sample below.
+      rng.key = stream_key_finish(sp.ind_key, (uint64_t)s);
+      rng.ctr = 0;
+      sb = (a.dbg >= 2) ? n : diffuse_sample_t(sp.ct < 0 ? -n : n, ld3(sp.perp), rng);
+    } else {
+      int pix, i, j, k;
+      uint64_t psample;
+      decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
+      rng.init(a.F.seed, KIND_IND, psample, (uint64_t)s);
+      sb = (a.dbg >= 2) ? n : diffuse_sample(n, sp.ct, rng);
+    }
     C3 Wt = ldc(sp.wt);  // kd / n_i (primary_kernel)
     if (a.dbg != 0) {
       P.base = rgb(sb.x, sb.y, sb.z);
@@ -745,7 +764,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
       } else {
         P.cnt.monte++;
         if (diffuse_only(a.S.mats[h.mat])) {
-          ind_shade<true>(P, h, org, dir, rng, Wt, tw);
+          ind_shade<true, true>(P, h, org, dir, rng, Wt, tw);  // tw is (1, 1, 1) here
         } else {
           // glass / mirror hit: shaded in ind_cont_kernel (wave-aggregated append)
           queue = true;
@@ -798,7 +817,22 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
     a.ind_qmask[t >> 6] = qm;
     a.ind_bmask[t >> 6] = bm;
   }
-  path_stats(a, cnt);
+  if (SPLIT) {
+    // Of the six -v counters the split kernel moves two, each by 0 or 1 per lane: `indirect`
+    // (the lane ran a sample) and `monte` (its ray hit). ind_shade<true> and put_query touch no
+    // counter, direct light is not evaluated here, and a queued lane's later counts are
+    // ind_cont_kernel's: shadow, trans, spec and caustic stay 0. Two ballots give the totals
+    // path_stats' three 64-bit wave reductions would.
+    const uint32_t ni = (uint32_t)__popcll(__ballot(cnt.indirect != 0u));
+    const uint32_t nm = (uint32_t)__popcll(__ballot(cnt.monte != 0u));
+    if ((threadIdx.x & 63) == 0) {
+      unsigned long long *sd = stat_stripe(a.stats);
+      if (ni) atomicAdd(sd + ST_INDIRECT, (unsigned long long)ni);
+      if (nm) atomicAdd(sd + ST_MONTE, (unsigned long long)nm);
+    }
+  } else {
+    path_stats(a, cnt);
+  }
 }
 
 // the queued indirect paths, one per thread: block b serves stripe b % IND_QS, striding over its
@@ -1919,7 +1953,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRIMARY_WPE
     const double2 *r = reinterpret_cast<const double2 *>(ray_slice(a).rays + b);
     const double2 r0 = r[0], r1 = r[1], r2 = r[2];
     V org = {r0.x, r0.y, r1.x}, dir = {r1.y, r2.x, r2.y};
-    primary_shade(a, b, org, dir, org, rng, c_ray, c_shadow, c_ind);
+    primary_shade(a, b, org, dir, org, psample, rng, c_ray, c_shadow, c_ind);
   }
   wave_add(&a.stats[ST_RAY], c_ray);
   wave_add(&a.stats[ST_SHADOW], c_shadow);

@@ -97,6 +97,10 @@ struct DMaterial {
   int32_t pad;
   // derived per-material constants used by the Monte Carlo loops (montecarlo.cpp:94-99)
   double max_kd, max_kt, max_ks, max_e;
+  // kd[c] * 1.0 / max_kd: the weight of a path's global-map query at its first hit, where the
+  // throughput is still exactly one (ind_shade). Filled by the loader with IEEE division, the
+  // device's own; left 0 when max_kd == 0 (the query branch rnd < max_kd is then never taken)
+  double kd_pd[3];
 };
 
 struct DLight {

@@ -109,6 +109,7 @@ static void mat_flags(DMaterial &m) {  // R3Brdf::UpdateFlags, R3Brdf.cpp:338-34
     return v;
   };
   m.max_kd = mx(m.kd); m.max_kt = mx(m.kt); m.max_ks = mx(m.ks); m.max_e = mx(m.e);
+  for (int i = 0; i < 3; i++) m.kd_pd[i] = (m.max_kd == 0.0) ? 0.0 : m.kd[i] * 1.0 / m.max_kd;
 }
 
 static DMaterial default_material() {  // R3default_brdf, R3Brdf.cpp:13-15
