@@ -378,6 +378,10 @@ struct gi_ctx {
   bool mc_sub = true;             // sub-paths' first bounce in mc_sub_kernel (GI_MC_SUB=0: all in ind_cont_kernel)
   int mc_persist = -1;            // Monte Carlo paths in mc_persist_kernel with this many blocks
                                   // (GI_MC_PERSIST; 0: mc_kernel, one path per lane; -1: auto)
+  int mc_wave = -1;               // Monte Carlo paths breadth first, this many single-bounce launches
+                                  // before the tail (GI_MC_WAVE; 0: off; -1: auto); a persistent
+                                  // grid asked for by number goes first
+  DBuf mc_wstate, mc_wlist, mc_wcount;  // its path states, live lists and counters (McWave)
   DBuf prim_rgb;                  // per-primary sums of the reduction
   DBuf d_rays, d_ray_ids;         // ray mode: the batch's rays and stream ids (gi_render_rays);
                                   // gi_camera_rays: one chunk of its output
@@ -1496,6 +1500,8 @@ int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &p
     const uint64_t ind_full = 64 * ((((uint64_t)a.tind + 63) / 64 + IND_QS - 1) / IND_QS);
     if (a.split_ind && a.total_ind > 0) HIPCHK(c, c->ind_ncont.ensure(IND_QS * 32 * 4));
     // Monte Carlo paths' indirect sub-paths: at most one per path, so the worst case is sized
+    McWave mwave;
+    memset(&mwave, 0, sizeof mwave);
     if (a.split_ind && a.total_mc > 0 && a.F.indirect) {
       const uint64_t full = 64 * ((((uint64_t)a.total_mc + 63) / 64 + IND_QS - 1) / IND_QS);
       HIPCHK(c, c->mc_cont.ensure((size_t)IND_QS * full * sizeof(IndCont)));
@@ -1508,7 +1514,23 @@ int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &p
       // was measured faster (C3 +5.5 %; with hard lights the plain kernel wins: C2 -0.4 %, C4
       // -7.4 %, since the persistent waves hold every SIMD's registers while the indirect kernel
       // on the other stream waits)
-      if (c->mc_persist > 0 || (c->mc_persist < 0 && !a.S.hard_lights)) {
+      // Breadth first (GI_MC_WAVE): by number wherever the persistent kernel is
+      // not asked for by number; by default (-1) 4 rounds for the class it was measured faster
+      // on, hard lights over triangles and spheres only (C2 -2.0 %; 4 and 8 rounds measured the
+      // same, 16 no better). Soft-light scenes keep the persistent kernel, the other hard-light
+      // element sets (whose step kernels spill) mc_kernel.
+      const bool wave_class = a.S.hard_lights && (a.S.kinds & ~KINDS_TRI_SPHERE) == 0;
+      const int rounds = c->mc_persist > 0 ? 0 : c->mc_wave >= 0 ? c->mc_wave : wave_class ? 4 : 0;
+      if (rounds > 0) {
+        HIPCHK(c, c->mc_wstate.ensure((size_t)a.total_mc * sizeof(McState)));
+        HIPCHK(c, c->mc_wlist.ensure(2 * (size_t)a.total_mc * 4));
+        HIPCHK(c, c->mc_wcount.ensure(((size_t)MC_WAVE_MAX_ROUNDS + 1) * 4));
+        mwave.state = c->mc_wstate.as<McState>();
+        mwave.list[0] = c->mc_wlist.as<uint32_t>();
+        mwave.list[1] = mwave.list[0] + a.total_mc;
+        mwave.count = c->mc_wcount.as<uint32_t>();
+        mwave.rounds = rounds;
+      } else if (c->mc_persist > 0 || (c->mc_persist < 0 && !a.S.hard_lights)) {
         a.mc_next = c->qcount.as<uint32_t>() + 2;
         a.mc_persist_blocks = c->mc_persist > 0 ? c->mc_persist : 1024;
       }
@@ -1566,7 +1588,8 @@ int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int32_t> &p
       a.qcount = c->qcount.as<uint32_t>();
       HIPCHK(c, hipMemcpyAsync(c->qcount.p, qbase, 8, hipMemcpyHostToDevice, c->stream));
       if (!a.tiled_skip && tind > (uint64_t)a.total_ind) launch_ind_pad(a, c->stream);  // (never when tind = 0)
-      launch_path(a, c->stream, c->stream2, c->ev_fork, c->ev_join, true);
+      launch_path(a, c->stream, c->stream2, c->ev_fork, c->ev_join, true,
+                  mwave.rounds > 0 ? &mwave : nullptr);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipMemcpyAsync(nq, c->qcount.p, 8, hipMemcpyDeviceToHost, c->stream));
       uint32_t fills[IND_QS * 32];
@@ -1795,6 +1818,7 @@ int gi_create(gi_ctx **out, int dev) {
   c->chunk_dk = env_num("GI_CHUNK_DK", c->chunk_dk) != 0;
   c->mc_sub = env_num("GI_MC_SUB", c->mc_sub) != 0;
   c->mc_persist = std::max(-1, (int)env_num("GI_MC_PERSIST", c->mc_persist));
+  c->mc_wave = std::min(MC_WAVE_MAX_ROUNDS, std::max(-1, (int)env_num("GI_MC_WAVE", c->mc_wave)));
   c->elem_pretest = env_num("GI_ELEM_PRETEST", c->elem_pretest) != 0;
   c->chunk_fb_all = env_num("GI_CHUNK_FB_ALL", c->chunk_fb_all) != 0;
   c->ind_frac = std::min(1.0, std::max(1e-6, env_num("GI_IND_FRAC", c->ind_frac)));
@@ -1893,7 +1917,8 @@ static void release_scratch(gi_ctx *c) {
                   &c->ind_off, &c->base, &c->pixels, &c->rgbf, &c->rgb8, &c->stats_bak,
                   &c->pcounts, &c->poffs, &c->pbuf, &c->pkeys, &c->pcursor, &c->ptmp, &c->pacc,
                   &c->pglob, &c->ind_cont, &c->ind_ncont, &c->mc_cont, &c->mc_ncont,
-                  &c->mc_cont2, &c->mc_ncont2, &c->prim_rgb, &c->ind_tab, &c->mc_tab,
+                  &c->mc_cont2, &c->mc_ncont2, &c->mc_wstate, &c->mc_wlist, &c->mc_wcount,
+                  &c->prim_rgb, &c->ind_tab, &c->mc_tab,
                   &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids,
                   &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
                   &c->dn_img[1], &c->rad_frame, &c->rad_samples, &c->rad_mean, &c->rad_var,

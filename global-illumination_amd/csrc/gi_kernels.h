@@ -69,6 +69,36 @@ constexpr uint32_t IND_EMPTY = 0xffffffffu;
 // chunk k-NN fallback list stripes: block b appends to stripe b % FB_QS
 constexpr int FB_QS = 64;
 
+// A Monte Carlo path between two bounces of the breadth-first schedule (mc_wave_begin_kernel /
+// mc_wave_step_kernel, GI_MC_WAVE): MonteCarlo_PathTrace's loop state (McLoop) and what the
+// path's context carries from one bounce to the next (PathCtx). Entry t belongs to path t of
+// the batch; its mc_cont stripe follows from t. The -v counters are not state: every launch
+// adds its own (integer sums are order-free).
+struct alignas(16) McState {
+  double org[3], dir[3], ray_start[3];
+  double tw[3], W[3];
+  double base[3];         // the path's sum so far
+  uint64_t rkey, rctr;    // RNG stream position
+  int64_t fixed[2];       // PathCtx::fixed
+  uint32_t g, prim;       // path slot, primary sample
+  uint32_t pslot, j;      // slot within the primary, queries issued so far
+  int32_t iter, hint;     // bounces done, triangle the current ray leaves from
+  uint32_t pad[2];
+};
+static_assert(sizeof(McState) == 208 && alignof(McState) == 16,
+              "path state record is 13 16-byte words");
+
+// The breadth-first schedule's buffers: launch k (0 = the begin kernel) appends its surviving
+// paths to list[k & 1] and counts them in count[k]; launch k + 1 reads both. One counter per
+// launch, all cleared by one fill before the first launch.
+struct McWave {
+  McState *state;      // [total_mc]
+  uint32_t *list[2];   // [total_mc] each: path indices t of the live paths
+  uint32_t *count;     // [rounds + 1]
+  int32_t rounds;      // single-bounce launches (the begin kernel's included); <= 0: off
+};
+constexpr int MC_WAVE_MAX_ROUNDS = 1024;
+
 struct QShade {
   double n[3];   // surface normal
   double ex[3];  // exact reflection direction (Phong lobe term)
@@ -396,8 +426,11 @@ void launch_primary(const RenderArgs &a, hipStream_t st);  // camera or ray mode
 void launch_camera_rays(const CameraRaysArgs &a, hipStream_t st);
 // wait_join = false: the join event is recorded on st2 but st does not wait for it (the caller
 // makes st wait later, after work that reads only the deterministic query slots)
+// mw with rounds > 0: the Monte Carlo paths run one bounce per launch (McWave) where their
+// sub-paths are deferred (a.mc_cont) and the persistent kernel is not asked for (a.mc_next)
 void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2 = nullptr,
-                 hipEvent_t fork = nullptr, hipEvent_t join = nullptr, bool wait_join = true);
+                 hipEvent_t fork = nullptr, hipEvent_t join = nullptr, bool wait_join = true,
+                 const McWave *mw = nullptr);
 // float4 queries {x, y, z, 0} at the photons of a map (KNN_MODE_DK input)
 void launch_photon_queries(const float *pos4, int64_t n, float4 *q, hipStream_t st);
 // dense copy of the striped chunk fallback list; total length to *total

@@ -410,6 +410,41 @@ __device__ __noinline__ void mc_indirect(PathCtx &P, V org, V dir, Rng &rng, C3 
   mc_indirect_body<KINDS>(P, org, dir, rng, W);
 }
 
+// List compaction for the breadth-first path schedules. Both take one atomic per wave (per
+// stripe), like put_query; the order of the entries within a list is free.
+//
+// Every lane of the wave calls this; the lanes with keep set append v to list (their count
+// added to *count by the first of them).
+__device__ __forceinline__ void wave_list_append(uint32_t *list, uint32_t *count, bool keep,
+                                                 uint32_t v) {
+  const uint64_t m = __ballot(keep);
+  if (m == 0) return;
+  const int lane = (int)(threadIdx.x & 63);
+  const int leader = __ffsll((long long)m) - 1;
+  uint32_t b = 0;
+  if (lane == leader) b = atomicAdd(count, (uint32_t)__popcll(m));
+  b = (uint32_t)__shfl((int)b, leader, 64);
+  if (keep) list[b + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
+}
+// The calling lanes (any subset of the wave) each take an entry of the striped queue whose
+// fill counters are fill[stripe * 32]: returns the lane's index within its stripe.
+__device__ __forceinline__ uint32_t wave_stripe_append(uint32_t *fill, uint32_t stripe) {
+  const int lane = (int)(threadIdx.x & 63);
+  uint64_t rem = __ballot(1);
+  uint32_t idx = 0;
+  while (rem) {  // one trip per stripe present
+    const int leader = __ffsll((long long)rem) - 1;
+    const uint32_t ls = (uint32_t)__shfl((int)stripe, leader, 64);
+    const uint64_t grp = __ballot(stripe == ls) & rem;
+    uint32_t b = 0;
+    if (lane == leader) b = atomicAdd(&fill[ls * 32], (uint32_t)__popcll(grp));
+    b = (uint32_t)__shfl((int)b, leader, 64);
+    if (stripe == ls) idx = b + (uint32_t)__popcll(grp & ((1ull << lane) - 1ull));
+    rem &= ~grp;
+  }
+  return idx;
+}
+
 // MonteCarlo_PathTrace's loop state (montecarlo.cpp:16-171): the current ray, the loop's
 // ray_start, the throughput, the path's outer weight and RNG stream, the iteration count
 struct McLoop {
@@ -430,8 +465,10 @@ __device__ __forceinline__ void mc_begin(McLoop &L, V org, V dir, const Rng &rng
 }
 
 // One iteration of MonteCarlo_PathTrace's loop (DEFER: indirect sub-paths go to the mc_cont
-// queue). Returns false when the path has ended.
-template <uint32_t KINDS = KINDS_ALL, bool DEFER = false, bool HARD = false>
+// queue). Returns false when the path has ended. MIXED: the lanes of a wave hold paths of
+// different mc_cont stripes (mc_wave_step_kernel), so the append takes one atomic per stripe
+// present among the wave's appending lanes instead of one per wave.
+template <uint32_t KINDS = KINDS_ALL, bool DEFER = false, bool HARD = false, bool MIXED = false>
 __device__ __forceinline__ bool mc_step(PathCtx &P, McLoop &L) {
   const SceneView &S = *P.S;
   const Flags &F = *P.F;
@@ -486,6 +523,9 @@ __device__ __forceinline__ bool mc_step(PathCtx &P, McLoop &L) {
         size_t e;
         if (P.cont_slot >= 0) {
           e = (size_t)P.cont_slot;  // mc_persist_kernel: the entry of path t is slot t
+        } else if (MIXED) {
+          e = (size_t)P.qstripe * P.A->mc_cap_s +
+              wave_stripe_append(P.A->mc_ncont, P.qstripe);
         } else {  // mc_kernel: one atomic per wave on its stripe
           int lane = (int)(threadIdx.x & 63);
           uint64_t act = __ballot(1);
@@ -1137,6 +1177,171 @@ void mc_persist_kernel(RenderArgs a) {
       cnt.spec += P.cnt.spec; cnt.indirect += P.cnt.indirect; cnt.caustic += P.cnt.caustic;
       active = false;
     }
+  }
+  path_stats(a, cnt);
+}
+
+// The same Monte Carlo paths breadth first (GI_MC_WAVE): one bounce per launch over a compacted
+// list of the live paths, their state in memory between launches (McState). Every lane of
+// every launch has a bounce to run, as in the persistent kernel, but the blocks are short and
+// retire as they go, so the other stream's blocks take their place as they do beside mc_kernel.
+// A path's arithmetic, RNG stream, query keys, base slot and mc_cont stripe depend on its index
+// t alone, so the image and counters equal mc_kernel's.
+//
+// Occupancy targets (waves per SIMD), triangle-and-sphere hard-light instances, C2 frame
+// (DESIGN.md 3.4). Step kernel: 250 VGPRs at 2; at 3 it spills 157 (368 B of scratch per lane)
+// and the frame is 8 ms slower. Begin kernel: 184 VGPRs at 2; at 3, 168 with 25 spilled (96 B)
+// and the frame 12 ms faster; at 4, 128 with 137 spilled: the kernel itself 3x faster, but
+// ind_kernel beside it 7 % slower and the frame 5 ms behind 3. Only that instance takes the
+// begin kernel's target: the compiler hands a kernel's occupancy target down to the
+// out-of-line functions it calls, and the soft-light instances share theirs (the shadow fan)
+// with mc_kernel and mc_persist_kernel. With every begin kernel at 3 those kernels traded their
+// 72-190 spilled VGPRs for 70-220 B more scratch per lane, and C3 went from 2,269 to 2,535 ms.
+#ifndef MC_WAVE_WPE
+#define MC_WAVE_WPE 2
+#endif
+#ifndef MC_WAVE_BEGIN_WPE
+#define MC_WAVE_BEGIN_WPE 3
+#endif
+__device__ __forceinline__ void mc_state_store(McState &s, const PathCtx &P, const McLoop &L) {
+  s.org[0] = L.org.x; s.org[1] = L.org.y; s.org[2] = L.org.z;
+  s.dir[0] = L.dir.x; s.dir[1] = L.dir.y; s.dir[2] = L.dir.z;
+  s.ray_start[0] = L.ray_start.x; s.ray_start[1] = L.ray_start.y; s.ray_start[2] = L.ray_start.z;
+  s.tw[0] = L.tw.r; s.tw[1] = L.tw.g; s.tw[2] = L.tw.b;
+  s.W[0] = L.W.r; s.W[1] = L.W.g; s.W[2] = L.W.b;
+  s.base[0] = P.base.r; s.base[1] = P.base.g; s.base[2] = P.base.b;
+  s.rkey = L.rng.key;
+  s.rctr = L.rng.ctr;
+  s.fixed[0] = P.fixed[0];
+  s.fixed[1] = P.fixed[1];
+  s.g = (uint32_t)P.g;
+  s.prim = P.prim;
+  s.pslot = P.pslot;
+  s.j = P.j;
+  s.iter = L.iter;
+  s.hint = P.hint;
+}
+__device__ __forceinline__ void mc_state_load(const McState &s, const RenderArgs &a, uint32_t t,
+                                              PathCtx &P, McLoop &L) {
+  path_init(P, a, (int64_t)s.g, (int64_t)s.prim, (int)s.pslot);
+  P.j = s.j;
+  P.base = ldc(s.base);
+  P.fixed[0] = s.fixed[0];
+  P.fixed[1] = s.fixed[1];
+  P.hint = s.hint;
+  P.qstripe = (t >> 6) & (IND_QS - 1);  // the stripe mc_kernel's wave of path t appends to
+  L.org = ld3(s.org);
+  L.dir = ld3(s.dir);
+  L.ray_start = ld3(s.ray_start);
+  L.tw = ldc(s.tw);
+  L.W = ldc(s.W);
+  L.rng.key = s.rkey;
+  L.rng.ctr = s.rctr;
+  L.iter = s.iter;
+}
+__device__ __forceinline__ void counts_add(Counts &c, const Counts &d) {
+  c.shadow += d.shadow; c.monte += d.monte; c.trans += d.trans;
+  c.spec += d.spec; c.indirect += d.indirect; c.caustic += d.caustic;
+}
+
+// mc_kernel's prologue and the path's first bounce (every path is live there, so the state
+// makes no round trip); the survivors' state is stored and their indices start list 0
+template <uint32_t KINDS, bool HARD, bool RAYS>
+__global__ __launch_bounds__(128)
+__attribute__((amdgpu_waves_per_eu((HARD && KINDS == KINDS_TRI_SPHERE) ? MC_WAVE_BEGIN_WPE : MC_WPE)))
+void mc_wave_begin_kernel(RenderArgs a, McWave w) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  Counts cnt = {0, 0, 0, 0, 0, 0};
+  bool alive = false;
+  if (t < a.total_mc) {
+    const SceneView &S = a.S;
+    const Flags &F = a.F;
+    int64_t pb = wave_owner(a.mc_off, a.nprim, t, a.total_mc, a.mc_tab);
+    int s = (int)(t - a.mc_off[pb]);
+    const Spawn &sp = a.spawn[pb];
+    int64_t g = (int64_t)a.path_off[pb] + 1 + s;
+    int pix, i, j, k;
+    uint64_t psample;
+    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
+    const DMaterial &m = S.mats[sp.mat];
+    V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
+    double ct = sp.ct, R = sp.R;
+    PathCtx P;
+    McLoop L;
+    path_init(P, a, g, pb, 1 + s);  // qstripe: this wave's, (t >> 6) % IND_QS
+    P.hint = sp.tri;
+    Rng rng;
+    V sb;
+    C3 wt;
+    if (s < sp.n_t) {
+      rng.init(F.seed, KIND_TRANS, psample, (uint64_t)s);
+      V ex = transmissive_bounce_nc(F.ir_air, n, view, ct, m.ir);
+      sb = F.distrib_trans ? specular_sample_call(ex, m.n, ct, rng) : ex;
+      wt = ((1.0 - R) * ldc(m.kt)) / (double)sp.n_t;
+      P.cnt.trans++;
+    } else {
+      s -= sp.n_t;
+      rng.init(F.seed, KIND_SPEC, psample, (uint64_t)s);
+      V ex = reflective_bounce(n, view, ct);
+      sb = F.distrib_spec ? specular_sample_call(ex, m.n, ct, rng) : ex;
+      wt = (ldc(m.kt) * R + ldc(m.ks)) / (double)sp.n_s;
+      P.cnt.spec++;
+    }
+    mc_begin(L, p + sb * kEps, sb, rng, wt);
+    if (!F.monte_carlo) L.iter = F.max_monte_depth;  // MonteCarlo_PathTrace returns at once
+    alive = mc_step<KINDS, true, HARD>(P, L);
+    if (alive) {
+      mc_state_store(w.state[t], P, L);
+    } else {
+      a.base[3 * g] = P.base.r;
+      a.base[3 * g + 1] = P.base.g;
+      a.base[3 * g + 2] = P.base.b;
+    }
+    cnt = P.cnt;
+  }
+  wave_list_append(w.list[0], w.count, alive, (uint32_t)t);
+  path_stats(a, cnt);
+}
+
+// One further bounce (TAIL: up to `steps`) of the paths of in_list[0, *in_count): a path that ends writes
+// its base as mc_kernel does, a survivor stores its state and goes to out_list. The grid may be
+// larger than the list (the host does not know its length): a wave with no entry exits.
+template <uint32_t KINDS, bool HARD, bool TAIL>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WAVE_WPE)))
+void mc_wave_step_kernel(RenderArgs a, McState *state, const uint32_t *in_list,
+                         const uint32_t *in_count, uint32_t *out_list, uint32_t *out_count,
+                         int steps) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t n = min((int64_t)*in_count, a.total_mc);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane;  // the wave's first entry
+  if (i0 >= n) return;
+  Counts cnt = {0, 0, 0, 0, 0, 0};
+  for (; i0 < n; i0 += stride) {
+    const int64_t i = i0 + lane;
+    bool alive = false;
+    uint32_t t = 0;
+    if (i < n) {
+      t = in_list[i];
+      PathCtx P;
+      McLoop L;
+      mc_state_load(state[t], a, t, P, L);
+      alive = true;
+      if (TAIL) {
+        for (int s = 0; s < steps && alive; s++) alive = mc_step<KINDS, true, HARD, true>(P, L);
+      } else {
+        alive = mc_step<KINDS, true, HARD, true>(P, L);
+      }
+      if (alive) {
+        mc_state_store(state[t], P, L);
+      } else {
+        a.base[3 * P.g] = P.base.r;
+        a.base[3 * P.g + 1] = P.base.g;
+        a.base[3 * P.g + 2] = P.base.b;
+      }
+      counts_add(cnt, P.cnt);
+    }
+    wave_list_append(out_list, out_count, alive, t);
   }
   path_stats(a, cnt);
 }
@@ -2044,6 +2249,22 @@ static void launch_mc_sub(const RenderArgs &a, hipStream_t st) {
   else
     mc_sub_kernel<KINDS_ALL><<<IND_QS * 32, 128, 0, st>>>(a, a.mc_cont, a.mc_ncont, a.mc_cap_s);
 }
+// The breadth-first Monte Carlo schedule: the begin kernel (prologue + first bounce), rounds - 1
+// launches of one bounce each over the ping-ponged live lists, and one launch that runs the
+// few survivors to the end. The live counts stay on the device: every launch has mc_kernel's
+// grid, and its waves past the list's length exit.
+template <uint32_t KINDS, bool HARD, bool RAYS>
+static void launch_mc_wave(const RenderArgs &a, const McWave &w, hipStream_t ms) {
+  const unsigned g = nblk(a.total_mc, 128);
+  mc_wave_begin_kernel<KINDS, HARD, RAYS><<<g, 128, 0, ms>>>(a, w);
+  for (int k = 1; k < w.rounds; k++)
+    mc_wave_step_kernel<KINDS, HARD, false><<<g, 128, 0, ms>>>(
+        a, w.state, w.list[(k - 1) & 1], w.count + (k - 1), w.list[k & 1], w.count + k, 1);
+  const int k = w.rounds;
+  mc_wave_step_kernel<KINDS, HARD, true><<<g, 128, 0, ms>>>(
+      a, w.state, w.list[(k - 1) & 1], w.count + (k - 1), w.list[k & 1], w.count + k,
+      std::max(1, a.F.max_monte_depth));
+}
 // Path expansion of one batch. The Monte Carlo paths (mc_kernel: few, long, one wave per SIMD
 // by its registers) run on the side stream st2 when given, concurrently with the indirect paths
 // on st, so their waves share the CUs instead of running as a low-occupancy tail; st waits for
@@ -2051,9 +2272,12 @@ static void launch_mc_sub(const RenderArgs &a, hipStream_t st) {
 // append queries through the same atomic counters.
 template <bool RAYS>
 static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_t fork,
-                          hipEvent_t join, bool wait_join) {
+                          hipEvent_t join, bool wait_join, const McWave *mw) {
   const bool side = st2 && fork && join && a.total_mc > 0;
   hipStream_t ms = side ? st2 : st;
+  const bool wave = mw && mw->rounds > 0 && a.total_mc > 0 && a.mc_cont && !a.mc_next;
+  // the live-list counters, like the queues' below: on st, before the fork
+  if (wave) (void)hipMemsetAsync(mw->count, 0, ((size_t)mw->rounds + 1) * sizeof(uint32_t), st);
   // the Monte Carlo queues' counters are zeroed on st before the fork: a fill on the side stream
   // waits for a CU slot behind st's kernels (rocprof: single fills of 42 ms at C2 and 170 ms
   // at C3 with the persistent kernel), and the side stream's kernels wait behind it
@@ -2089,6 +2313,16 @@ static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, 
         else mc_persist_kernel<KINDS_POLY, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
       } else {
         mc_persist_kernel<KINDS_ALL, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
+      }
+    } else if (wave) {
+      if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
+        if (a.S.hard_lights) launch_mc_wave<KINDS_TRI_SPHERE, true, RAYS>(a, *mw, ms);
+        else launch_mc_wave<KINDS_TRI_SPHERE, false, RAYS>(a, *mw, ms);
+      } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
+        if (a.S.hard_lights) launch_mc_wave<KINDS_POLY, true, RAYS>(a, *mw, ms);
+        else launch_mc_wave<KINDS_POLY, false, RAYS>(a, *mw, ms);
+      } else {
+        launch_mc_wave<KINDS_ALL, false, RAYS>(a, *mw, ms);
       }
     } else if (a.mc_cont) {
       if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
@@ -2127,9 +2361,9 @@ static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, 
   }
 }
 void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2, hipEvent_t fork,
-                 hipEvent_t join, bool wait_join) {
-  if (a.spp) launch_path_t<true>(a, st, st2, fork, join, wait_join);
-  else launch_path_t<false>(a, st, st2, fork, join, wait_join);
+                 hipEvent_t join, bool wait_join, const McWave *mw) {
+  if (a.spp) launch_path_t<true>(a, st, st2, fork, join, wait_join, mw);
+  else launch_path_t<false>(a, st, st2, fork, join, wait_join, mw);
 }
 // Shard gather of a device set (gi_host.cpp render_multi): a device's output pixels packed in
 // its pixel-list order as {r, g, b, rgb8 bytes} (16 B), and their scatter on the first device.
