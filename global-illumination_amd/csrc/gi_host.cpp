@@ -450,6 +450,9 @@ struct gi_ctx {
   // feature planes (gi_camera_features / gi_ray_features): one chunk of sample records and of
   // planes; denoise pass (gi_denoise): the frame's floats, its planes, the two ping-pong images
   DBuf feat_samples, feat_planes, dn_rgbf, dn_planes, dn_img[2];
+  // variance-guided denoise (gi_denoise_radiance, gi_accum_denoise): the uploaded channel
+  // variances and the filtered luminance-variance plane; the rest is gi_denoise's scratch
+  DBuf vdn_var, vdn_vlum;
   // radiance frames (gi_render_radiance, gi_render_rays_radiance, gi_accum_add_*): while rad_on,
   // render_pixels launches reduce_radiance_kernel beside reduce_kernel; rad_frame holds the pass's
   // {m, M2} (six doubles per pixel), rad_samples the samples when the caller asked for them
@@ -1921,7 +1924,8 @@ static void release_scratch(gi_ctx *c) {
                   &c->prim_rgb, &c->ind_tab, &c->mc_tab,
                   &c->ind_trows, &c->ind_rows, &c->ind_masks, &c->pack, &c->d_rays, &c->d_ray_ids,
                   &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
-                  &c->dn_img[1], &c->rad_frame, &c->rad_samples, &c->rad_mean, &c->rad_var,
+                  &c->dn_img[1], &c->vdn_var, &c->vdn_vlum, &c->rad_frame, &c->rad_samples,
+                  &c->rad_mean, &c->rad_var,
                   &c->acc_part, &c->tile_err, &c->tile_nmin, &c->tile_mask, &c->tm_in, &c->tm_out};
   for (DBuf *b : bufs) b->release();
   std::vector<gi_ray>().swap(c->ray_stage);
@@ -3223,6 +3227,136 @@ int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, dou
   for (double v : part) sum += v;  // in block order: the result is reproducible bit for bit
   *noise = sum / (double)npix;
   return GI_OK;
+}
+
+// ---- variance-guided denoise (gi_denoise.hip vdenoise_*; no reference counterpart) --------
+void gi_vdenoise_params_default(gi_vdenoise_params *p) {
+  if (!p) return;
+  p->levels = 5;
+  p->normal_power_log2 = 5;
+  p->sigma_lum = 4.0;
+  p->sigma_depth = 0.05;
+  p->sigma_albedo = 0.1;
+  p->variance_floor = 1e-6;
+}
+
+// pp (null: defaults) checked into P
+static int vdenoise_params(gi_ctx *c, const gi_vdenoise_params *pp, gi_vdenoise_params &P) {
+  gi_vdenoise_params_default(&P);
+  if (pp) P = *pp;
+  if (P.levels < 1 || P.levels > 8) return fail(c, GI_ERR_ARG, "vdenoise: levels outside 1..8");
+  if (P.normal_power_log2 < 0 || P.normal_power_log2 > 8)
+    return fail(c, GI_ERR_ARG, "vdenoise: normal_power_log2 outside 0..8");
+  for (double s : {P.sigma_lum, P.sigma_depth, P.sigma_albedo, P.variance_floor})
+    if (!std::isfinite(s) || !(s > 0.0))
+      return fail(c, GI_ERR_ARG, "vdenoise: sigmas and variance_floor must be finite and positive");
+  return GI_OK;
+}
+
+// The levels over c->dn_img[0] (packed {r, g, b, v0}) and the planes uploaded from feat, then the
+// outputs (either may be null) to the host.
+static int vdenoise_levels(gi_ctx *c, int w, int h, const gi_pixel_features *feat,
+                           const gi_vdenoise_params &P, float *out_mean, float *out_vlum,
+                           double *kernel_ms) {
+  const size_t npix = (size_t)w * h;
+  HIPCHK(c, upload(c->dn_planes, feat, npix * sizeof(gi_pixel_features), c->stream));
+  HIPCHK(c, c->dn_img[1].ensure(npix * sizeof(float4)));
+  if (out_mean) HIPCHK(c, c->dn_rgbf.ensure(npix * 12));
+  if (out_vlum) HIPCHK(c, c->vdn_vlum.ensure(npix * 4));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+      hipEventDestroy(e0);
+      return fail(c, GI_ERR_HIP, "vdenoise: hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, c->stream);
+  }
+  VDenoiseArgs a;
+  memset(&a, 0, sizeof a);
+  a.W = w;
+  a.H = h;
+  a.npow = P.normal_power_log2;
+  a.sl2 = P.sigma_lum * P.sigma_lum;
+  a.vfloor = P.variance_floor;
+  a.sd2 = P.sigma_depth * P.sigma_depth;
+  a.isa2 = 1.0 / (P.sigma_albedo * P.sigma_albedo);
+  a.planes = c->dn_planes.as<float4>();
+  int cur = 0;
+  hipError_t le = hipSuccess;
+  for (int l = 0; l < P.levels && le == hipSuccess; l++) {
+    a.step = 1 << l;
+    a.src = c->dn_img[cur].as<float4>();
+    a.dst = c->dn_img[cur ^ 1].as<float4>();
+    launch_vdenoise_level(a, c->stream);
+    le = hipGetLastError();
+    cur ^= 1;
+  }
+  if (kernel_ms) (void)hipEventRecord(e1, c->stream);
+  if (le == hipSuccess) {
+    launch_vdenoise_unpack(c->dn_img[cur].as<float4>(), (int64_t)npix,
+                           out_mean ? c->dn_rgbf.as<float>() : nullptr,
+                           out_vlum ? c->vdn_vlum.as<float>() : nullptr, c->stream);
+    le = hipGetLastError();
+  }
+  if (le == hipSuccess && out_mean)
+    le = hipMemcpyAsync(out_mean, c->dn_rgbf.p, npix * 12, hipMemcpyDeviceToHost, c->stream);
+  if (le == hipSuccess && out_vlum)
+    le = hipMemcpyAsync(out_vlum, c->vdn_vlum.p, npix * 4, hipMemcpyDeviceToHost, c->stream);
+  if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
+  if (kernel_ms) {
+    float ms = 0.f;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    *kernel_ms = ms;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  HIPCHK(c, le);
+  return GI_OK;
+}
+
+int gi_denoise_radiance(gi_ctx *c, int w, int h, const float *mean, const float *variance,
+                        const gi_pixel_features *feat, const gi_vdenoise_params *pp, float *out_mean,
+                        float *out_vlum, double *kernel_ms) {
+  if (!c) return GI_ERR_ARG;
+  if (!mean || !variance || !feat || (!out_mean && !out_vlum))
+    return fail(c, GI_ERR_ARG, "null image buffer");
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(c, GI_ERR_ARG, "bad image size");
+  gi_vdenoise_params P;
+  int rc = vdenoise_params(c, pp, P);
+  if (rc) return rc;
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)w * h;
+  HIPCHK(c, upload(c->dn_rgbf, mean, npix * 12, c->stream));
+  HIPCHK(c, upload(c->vdn_var, variance, npix * 12, c->stream));
+  HIPCHK(c, c->dn_img[0].ensure(npix * sizeof(float4)));
+  launch_vdenoise_pack(c->dn_rgbf.as<float>(), c->vdn_var.as<float>(), (int64_t)npix,
+                       c->dn_img[0].as<float4>(), c->stream);
+  HIPCHK(c, hipGetLastError());
+  return vdenoise_levels(c, w, h, feat, P, out_mean, out_vlum, kernel_ms);
+}
+
+int gi_accum_denoise(gi_ctx *c, const gi_pixel_features *feat, const gi_vdenoise_params *pp,
+                     float *out_mean, float *out_vlum, double *kernel_ms) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (rc) return rc;
+  if (!feat || (!out_mean && !out_vlum)) return fail(c, GI_ERR_ARG, "null image buffer");
+  gi_vdenoise_params P;
+  rc = vdenoise_params(c, pp, P);
+  if (rc) return rc;
+  DeviceScope dev(c->device);
+  int64_t least = c->acc_n;
+  if (!c->acc_uniform && (rc = count_stats(c, &least, nullptr))) return rc;
+  if (least < 2)
+    return fail(c, GI_ERR_STATE, "vdenoise: every pixel of the accumulator needs at least 2 samples");
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  HIPCHK(c, c->dn_img[0].ensure(npix * sizeof(float4)));
+  launch_vdenoise_pack_accum(c->acc.as<double>(), c->acc_cnt.as<int64_t>(), (int64_t)npix,
+                             c->dn_img[0].as<float4>(), c->stream);
+  HIPCHK(c, hipGetLastError());
+  return vdenoise_levels(c, c->acc_w, c->acc_h, feat, P, out_mean, out_vlum, kernel_ms);
 }
 
 int gi_tonemap(gi_ctx *c, int w, int h, const float *radiance, double exposure, double white,

@@ -12,6 +12,8 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
                    and denoise pass")
   accum_select / accum_add_tiles / accum_add_adaptive / accum_get_counts: adaptive passes over
                    the noisy tiles of the accumulator (gi.h "adaptive passes")
+  denoise_radiance / accum_denoise: the variance-guided denoise of a radiance frame and of
+                   the accumulator (gi.h "variance-guided denoise")
   render_radiance / render_rays_radiance / accum_* / tonemap / write_image_float: unclamped
                    radiance frames with their variance, accumulation over passes and the tone
                    map (no reference counterpart; gi.h "radiance frames, accumulation over
@@ -48,6 +50,7 @@ EXPORTED = [
     "gi_accum_add_rays", "gi_accum_get", "gi_tonemap", "gi_radiance_bench",
     "gi_accum_get_counts", "gi_adaptive_params_default", "gi_accum_select", "gi_accum_add_tiles",
     "gi_accum_add_adaptive", "gi_adaptive_bench",
+    "gi_vdenoise_params_default", "gi_denoise_radiance", "gi_accum_denoise",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
@@ -100,6 +103,13 @@ class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32),
                 ("sigma_color", C.c_double), ("sigma_depth", C.c_double),
                 ("sigma_albedo", C.c_double)]
+
+
+class VDenoiseParams(C.Structure):
+    """gi_vdenoise_params"""
+    _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_lum", C.c_double), ("sigma_depth", C.c_double),
+                ("sigma_albedo", C.c_double), ("variance_floor", C.c_double)]
 
 
 class AdaptiveParams(C.Structure):
@@ -232,6 +242,13 @@ def lib():
                                             P(C.c_int64), P(RenderStats)]
         L.gi_adaptive_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         P(C.c_double), P(C.c_double), P(C.c_double)]
+        L.gi_vdenoise_params_default.argtypes = [P(VDenoiseParams)]
+        L.gi_vdenoise_params_default.restype = None
+        L.gi_denoise_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, P(VDenoiseParams), C.c_void_p, C.c_void_p,
+                                          P(C.c_double)]
+        L.gi_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, P(VDenoiseParams), C.c_void_p,
+                                       C.c_void_p, P(C.c_double)]
         L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                  C.c_double, C.c_void_p, C.c_void_p]
         L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -264,6 +281,17 @@ def default_params():
 def default_denoise_params():
     p = DenoiseParams()
     lib().gi_denoise_params_default(C.byref(p))
+    return p
+
+
+def default_vdenoise_params(**kw):
+    """gi_vdenoise_params: the defaults (gi_vdenoise_params_default) with the given fields set."""
+    p = VDenoiseParams()
+    lib().gi_vdenoise_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(VDenoiseParams._fields_):
+            raise TypeError(f"unknown vdenoise parameter {k}")
+        setattr(p, k, v)
     return p
 
 
@@ -632,6 +660,43 @@ class Renderer:
                                             C.byref(t[0]), C.byref(t[1]), C.byref(t[2])))
         return {"select_ms": t[0].value, "masked_merge_ms": t[1].value,
                 "accum_merge_ms": t[2].value}
+
+    def denoise_radiance(self, mean, variance, feat, **params):
+        """Variance-guided a-trous filter of a radiance frame (gi_denoise_radiance): mean and
+        variance of the mean [H, W, 3] as render_radiance / accum_get return them, feat [H, W];
+        params: fields of gi_vdenoise_params that differ from the defaults. Returns (filtered
+        mean [H, W, 3] float32, filtered luminance variance [H, W] float32, kernel_ms)."""
+        mean = np.ascontiguousarray(mean, dtype=np.float32)
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        h, w = feat.shape
+        if mean.shape != (h, w, 3) or variance.shape != (h, w, 3):
+            raise ValueError(f"frames {mean.shape}, {variance.shape} do not match planes "
+                             f"{feat.shape}")
+        p = default_vdenoise_params(**params)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        vlum = np.zeros((h, w), dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._check(lib().gi_denoise_radiance(self._ctx, w, h, mean.ctypes.data,
+                                              variance.ctypes.data, feat.ctypes.data, C.byref(p),
+                                              out.ctypes.data, vlum.ctypes.data, C.byref(ms)))
+        return out, vlum, ms.value
+
+    def accum_denoise(self, feat, **params):
+        """The same filter of the accumulator as it stands, read on the device and left
+        unchanged (gi_accum_denoise); feat: the planes of the accumulator's frame. Returns like
+        denoise_radiance."""
+        feat = np.ascontiguousarray(feat, dtype=FEATURE_DTYPE)
+        w, h = getattr(self, "_accum_size", (0, 0))
+        if w and feat.shape != (h, w):
+            raise ValueError(f"planes {feat.shape} do not match the accumulator's {(h, w)}")
+        p = default_vdenoise_params(**params)
+        out = np.zeros(feat.shape + (3,), dtype=np.float32)
+        vlum = np.zeros(feat.shape, dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._check(lib().gi_accum_denoise(self._ctx, feat.ctypes.data, C.byref(p),
+                                           out.ctypes.data, vlum.ctypes.data, C.byref(ms)))
+        return out, vlum, ms.value
 
     def tonemap(self, radiance, exposure=1.0, white=0.0, want_float=False):
         """Exposure, extended Reinhard curve (white > 0; 0: linear) and clamp of a radiance frame

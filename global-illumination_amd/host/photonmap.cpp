@@ -16,6 +16,10 @@
 // Extension: -adaptive [TILE] (TILE 4..64, default 8), only together with -noise T: whole-frame
 // passes until every pixel has the default min_samples, then gi_accum_add_adaptive passes with
 // threshold T over TILE x TILE tiles, until no tile is active or -passes is used up.
+// Extension: -vdenoise L (1..8, not with -denoise): counts as one of the radiance flags; after the
+// passes the accumulator is filtered by L levels of the variance-guided pass over its feature
+// planes (gi_camera_features + gi_accum_denoise, other parameters default) and the written image
+// is gi_tonemap of the filtered mean. -radiance FILE still receives the unfiltered mean.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -68,11 +72,11 @@ static bool TakeCamera(int &argc, char **argv, gi_camera &cam, bool &have) {
   return true;
 }
 
-// Takes `-denoise L` out of argv in the same way; false on a missing, non-integer or
-// out-of-range (1..8) L. The last -denoise wins.
-static bool TakeDenoise(int &argc, char **argv, int &levels) {
+// Takes `-denoise L` (or `-vdenoise L`: flag) out of argv in the same way; false on a missing,
+// non-integer or out-of-range (1..8) L. The last one wins.
+static bool TakeDenoise(int &argc, char **argv, int &levels, const char *flag = "-denoise") {
   for (int a = 1; a < argc;) {
-    if (strcmp(argv[a], "-denoise")) { a++; continue; }
+    if (strcmp(argv[a], flag)) { a++; continue; }
     if (a + 1 >= argc) return false;
     char *end = nullptr;
     const long v = strtol(argv[a + 1], &end, 10);
@@ -191,11 +195,17 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Invalid program argument: -denoise");
     return 1;
   }
+  int vdenoise_levels = 0;  // 0: no variance-guided denoise pass
+  if (!TakeDenoise(argc, argv, vdenoise_levels, "-vdenoise") || (vdenoise_levels && denoise_levels)) {
+    fprintf(stderr, "Invalid program argument: -vdenoise");
+    return 1;
+  }
   RadianceFlags rad;
   if (const char *bad = TakeRadiance(argc, argv, rad)) {
     fprintf(stderr, "Invalid program argument: %s", bad);
     return 1;
   }
+  if (vdenoise_levels) rad.any = true;
   gi_params P;
   gi_params_default(&P);
   const char *scene = nullptr, *out = nullptr, *err = nullptr;
@@ -229,7 +239,7 @@ int main(int argc, char **argv) {
     if (ds.count == 0) ds.count = 1;
   }
   if (rad.any && ds.count > 1) {
-    fprintf(stderr, "-passes, -noise, -exposure, -white and -radiance render on one device: not with -gpus %d\n",
+    fprintf(stderr, "-passes, -noise, -exposure, -white, -radiance and -vdenoise render on one device: not with -gpus %d\n",
             ds.count);
     return -1;
   }
@@ -290,7 +300,7 @@ int main(int argc, char **argv) {
   std::vector<float> mean(rad.any ? (size_t)w * h * 3 : 0);
   int passes_done = 0;
   long long acc_n = 0, acc_total = 0, acc_max = 0;
-  double acc_noise = 0.0;
+  double acc_noise = 0.0, vdenoise_ms = 0.0;
   if (rad.any) {
     // passes under seed, seed + 1, ... from the same maps, folded into the accumulator; the
     // written image is the tone-mapped unclamped mean
@@ -337,8 +347,19 @@ int main(int argc, char **argv) {
       for (int64_t v : counts) acc_max = v > acc_max ? v : acc_max;
     }
     int64_t n = 0;
-    ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK &&
-         gi_tonemap(ctx, w, h, mean.data(), rad.exposure, rad.white, rgbf.data(), rgb.data()) == GI_OK;
+    ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK;
+    std::vector<float> filtered;  // -vdenoise: the written image is the tone-mapped filtered mean
+    if (ok && vdenoise_levels) {
+      std::vector<gi_pixel_features> feat((size_t)w * h);
+      gi_vdenoise_params vp;
+      gi_vdenoise_params_default(&vp);
+      vp.levels = vdenoise_levels;
+      filtered.resize((size_t)w * h * 3);
+      ok = gi_camera_features(ctx, aa, w, h, feat.data()) == GI_OK &&
+           gi_accum_denoise(ctx, feat.data(), &vp, filtered.data(), nullptr, &vdenoise_ms) == GI_OK;
+    }
+    ok = ok && gi_tonemap(ctx, w, h, vdenoise_levels ? filtered.data() : mean.data(), rad.exposure,
+                          rad.white, rgbf.data(), rgb.data()) == GI_OK;
     acc_n = n;
     gi_set_params(ctx, &P);
     if (!ok) {
@@ -386,6 +407,8 @@ int main(int argc, char **argv) {
       printf("Accumulated image: %d passes, N = %lld samples per pixel, noise = %.6g\n", passes_done,
              acc_n, acc_noise);
     if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);
+    if (vdenoise_levels)
+      printf("Variance-guided denoise: %d levels, %.3f ms\n", vdenoise_levels, vdenoise_ms);
     fflush(stdout);
   }
   gi_destroy(ctx);

@@ -430,6 +430,65 @@ int gi_accum_add_tiles(gi_ctx *ctx, int aa, int tile_px, const uint8_t *mask,
  * selection. Errors as those two. */
 int gi_accum_add_adaptive(gi_ctx *ctx, int aa, const gi_adaptive_params *p, uint8_t *mask,
                           int64_t *active_pixels, gi_render_stats *stats);
+/* ---- variance-guided denoise of radiance frames and of the accumulator --------------------- */
+/* An a-trous filter like gi_denoise whose colour stop is each pixel's own standard error instead
+ * of a fixed sigma: it takes unclamped radiance with its variance of the mean, filters a noisy
+ * pixel widely and a converged one barely, and returns the variance that is left (DESIGN.md
+ * "Variance-guided denoise"; tests/vdenoise_ref.py restates it and the device equals it bit for
+ * bit). No reference counterpart. fp64 on float32 inputs, one IEEE operation per step in the
+ * order written, only + - * / max.
+ *
+ * Inputs: colour c (W*H*3 floats), the channels' variances of the mean (W*H*3 floats, >= 0) and
+ * the frame's planes. Per pixel v = (float)(0.2126^2 v_r + 0.7152^2 v_g + 0.0722^2 v_b), each
+ * squared weight one product, summed left to right. For level l = 0 .. levels-1, s = 2^l:
+ *   Y(c) = 0.2126 r + 0.7152 g + 0.0722 b, summed left to right;
+ *   g_p  = sum h3 v_q / sum h3 over q = p + (i, j), j = -1..1 outer, i = -1..1 inner, inside the
+ *          image, h3 = k3[|i|] k3[|j|], k3 = {1/2, 1/4};
+ *   il_p = 1 / (sigma_lum^2 g_p + variance_floor)   (g_p, il_p stay fp64);
+ *   taps q = p + s (i, j), j = -2..2 outer, i = -2..2 inner, inside the image, h = k[|i|] k[|j|],
+ *   k = {3/8, 1/4, 1/16}; covered means coverage > 0;
+ *     centre tap: w = h;   exactly one of p, q covered: the tap is skipped;
+ *     neither covered: w = h / (1 + xl);
+ *     both covered:    w = ((h m) zz) / (((1 + xl) (zz + dz dz)) (1 + xa));
+ *     xl = (dY dY) il_p, dY = Y(c_p) - Y(c_q);  m = max(0, n_p . n_q) squared normal_power_log2
+ *     times;  dz = z_p - z_q, zs = z_p + z_q, zz = sigma_depth^2 (zs zs);  xa = |a_p - a_q|^2
+ *     (summed r, g, b) * isa2, isa2 = 1 / (sigma_albedo sigma_albedo);
+ *   c'_p = sum w c_q / sum w per channel,  v'_p = sum (w w) v_q / ((sum w) (sum w)), both rounded
+ *   to float32; the next level reads the rounded values. sigma_lum is not halved per level: the
+ *   variance shrinks instead. sum w >= 9/64.
+ * Accepted limits: a pixel of variance 0 (a single sample, or clamped by the caller) counts as
+ * converged and is barely filtered; the inputs are not scanned for NaN / Inf or negative
+ * variances; no albedo demodulation (albedo is per material here and the albedo stop already
+ * separates materials); one device. */
+typedef struct gi_vdenoise_params {
+  int32_t levels;             /* 1..8 a-trous levels, step 2^l            default 5    */
+  int32_t normal_power_log2;  /* 0..8: normal weight = max(0,n.n)^(2^e)   default 5    */
+  double sigma_lum;           /* luminance stop, in standard errors       default 4.0  */
+  double sigma_depth;         /* relative depth difference                default 0.05 */
+  double sigma_albedo;        /*                                          default 0.1  */
+  double variance_floor;      /* added to sigma_lum^2 g                   default 1e-6 */
+} gi_vdenoise_params;
+void gi_vdenoise_params_default(gi_vdenoise_params *p);
+/* The filter of a frame given by the caller: mean, variance as gi_render_radiance / gi_accum_get
+ * return them. out_mean (W*H*3 floats) and out_variance_lum (W*H floats, the filtered luminance
+ * variance): either may be NULL, not both. p == NULL: defaults. kernel_ms (optional): summed
+ * HIP-event time of the level launches. GI_ERR_ARG for null buffers, width or height < 1, width *
+ * height >= 2^31, levels or normal_power_log2 out of range, or a sigma or variance_floor that is
+ * not finite and positive. Needs only a context (no scene); on a device set it runs on the first
+ * device. */
+int gi_denoise_radiance(gi_ctx *ctx, int width, int height, const float *mean,
+                        const float *variance, const gi_pixel_features *feat,
+                        const gi_vdenoise_params *p /* NULL: defaults */, float *out_mean,
+                        float *out_variance_lum, double *kernel_ms);
+/* The filter of the accumulator as it stands, read on the device: c = (float)mu, v_c = (float)(A /
+ * (N - 1) / N) under the pixel's own N, exactly what gi_accum_get returns, so the result equals
+ * gi_denoise_radiance of gi_accum_get's mean and variance bit for bit. feat: the planes of the
+ * accumulator's W x H frame. The accumulator is left bit for bit unchanged. GI_ERR_STATE before
+ * gi_accum_reset and while the smallest per-pixel count is < 2 (no variance yet);
+ * GI_ERR_UNSUPPORTED on a device set; GI_ERR_ARG as above. */
+int gi_accum_denoise(gi_ctx *ctx, const gi_pixel_features *feat, const gi_vdenoise_params *p,
+                     float *out_mean, float *out_variance_lum, double *kernel_ms);
+
 /* Tone map of a radiance frame (W*H*3 floats), per channel in fp64: x = exposure * c;
  * y = x * (1 + x / (white * white)) / (1 + x) when white > 0 (extended Reinhard: `white` maps to
  * 1), y = x when white == 0; clamped to [0, 1], rounded to float32. Linear output, as the
