@@ -466,6 +466,10 @@ struct gi_ctx {
   int64_t acc_n = 0;
   bool acc_valid = false, acc_uniform = true;
   DBuf tile_err, tile_nmin, tile_mask;  // adaptive passes: per tile error, smallest count, mask
+  // reprojection (gi_accum_reproject): the second accumulator and count plane the kernel writes
+  // (swapped with acc / acc_cnt afterwards; allocated on first use and kept like them) and the two
+  // uploaded plane sets (scratch)
+  DBuf acc2, acc2_cnt, rp_prev, rp_cur;
   DBuf tm_in, tm_out;             // gi_tonemap
 };
 
@@ -510,6 +514,24 @@ Flags make_flags(const gi_params &P) {
   return F;
 }
 
+// render.cpp:67-77: the camera block of the render kernels (and what gi_get_view returns)
+DCamera make_camera(const HostScene &H, const gi_params &P) {
+  DCamera cam;
+  memset(&cam, 0, sizeof cam);
+  double tx = tan(H.xfov), ty = tan(H.yfov);
+  double ul = sqrt(H.up[0] * H.up[0] + H.up[1] * H.up[1] + H.up[2] * H.up[2]);
+  double rl = sqrt(H.right[0] * H.right[0] + H.right[1] * H.right[1] + H.right[2] * H.right[2]);
+  for (int i = 0; i < 3; i++) {
+    cam.eye[i] = H.eye[i];
+    cam.far_org[i] = H.eye[i] + H.towards[i] * P.focus_depth;
+    cam.far_right[i] = H.right[i] * tx * P.focus_depth;
+    cam.far_up[i] = H.up[i] * ty * P.focus_depth;
+    cam.dof_u[i] = (ul == 0.0 ? H.up[i] : H.up[i] / ul) * P.aperture_radius;
+    cam.dof_v[i] = (rl == 0.0 ? H.right[i] : H.right[i] / rl) * P.aperture_radius;
+  }
+  return cam;
+}
+
 SceneView make_view(gi_ctx *c) {
   SceneView S;
   memset(&S, 0, sizeof S);
@@ -550,19 +572,7 @@ SceneView make_view(gi_ctx *c) {
     S.ambient[i] = H.ambient[i];
     S.background[i] = H.background[i];
   }
-  // render.cpp:67-77
-  const gi_params &P = c->P;
-  double tx = tan(H.xfov), ty = tan(H.yfov);
-  double ul = sqrt(H.up[0] * H.up[0] + H.up[1] * H.up[1] + H.up[2] * H.up[2]);
-  double rl = sqrt(H.right[0] * H.right[0] + H.right[1] * H.right[1] + H.right[2] * H.right[2]);
-  for (int i = 0; i < 3; i++) {
-    S.cam.eye[i] = H.eye[i];
-    S.cam.far_org[i] = H.eye[i] + H.towards[i] * P.focus_depth;
-    S.cam.far_right[i] = H.right[i] * tx * P.focus_depth;
-    S.cam.far_up[i] = H.up[i] * ty * P.focus_depth;
-    S.cam.dof_u[i] = (ul == 0.0 ? H.up[i] : H.up[i] / ul) * P.aperture_radius;
-    S.cam.dof_v[i] = (rl == 0.0 ? H.right[i] : H.right[i] / rl) * P.aperture_radius;
-  }
+  S.cam = make_camera(H, c->P);
   return S;
 }
 
@@ -1926,7 +1936,8 @@ static void release_scratch(gi_ctx *c) {
                   &c->feat_samples, &c->feat_planes, &c->dn_rgbf, &c->dn_planes, &c->dn_img[0],
                   &c->dn_img[1], &c->vdn_var, &c->vdn_vlum, &c->rad_frame, &c->rad_samples,
                   &c->rad_mean, &c->rad_var,
-                  &c->acc_part, &c->tile_err, &c->tile_nmin, &c->tile_mask, &c->tm_in, &c->tm_out};
+                  &c->acc_part, &c->tile_err, &c->tile_nmin, &c->tile_mask, &c->tm_in, &c->tm_out,
+                  &c->rp_prev, &c->rp_cur};
   for (DBuf *b : bufs) b->release();
   std::vector<gi_ray>().swap(c->ray_stage);
   std::vector<uint64_t>().swap(c->id_stage);
@@ -1975,7 +1986,8 @@ void gi_destroy(gi_ctx *c) {
   hipSetDevice(c->device);
   release_scratch(c);
   DBuf *bufs[] = {&c->d_nodes, &c->d_elems, &c->d_shapes, &c->d_tris, &c->d_bvh, &c->d_mats,
-                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount, &c->acc, &c->acc_cnt};
+                  &c->d_lights, &c->d_lut, &c->d_stats, &c->qcount, &c->acc, &c->acc_cnt,
+                  &c->acc2, &c->acc2_cnt};
   for (DBuf *b : bufs) b->release();
   for (int m = 0; m < 2; m++) {
     MapExec &X = c->mx[m];
@@ -2041,6 +2053,19 @@ int gi_get_camera(const gi_ctx *c, gi_camera *out) {
     out->up[i] = r[6 + i];
   }
   out->xfov = r[9];
+  return GI_OK;
+}
+
+int gi_get_view(const gi_ctx *c, gi_view *out) {
+  if (!c || !out) return GI_ERR_ARG;
+  if (!c->have_scene) return GI_ERR_STATE;
+  const DCamera cam = make_camera(c->scene, c->P);
+  for (int i = 0; i < 3; i++) {
+    out->eye[i] = cam.eye[i];
+    out->far_org[i] = cam.far_org[i];
+    out->far_right[i] = cam.far_right[i];
+    out->far_up[i] = cam.far_up[i];
+  }
   return GI_OK;
 }
 
@@ -2926,6 +2951,10 @@ int gi_accum_reset(gi_ctx *c, int w, int h) {
   const size_t npix = (size_t)w * h;
   HIPCHK(c, c->acc.ensure(npix * 48));
   HIPCHK(c, c->acc_cnt.ensure(npix * 8));
+  if (c->acc2.p) {  // the reprojection's second buffer follows the accumulator's size
+    HIPCHK(c, c->acc2.ensure(npix * 48));
+    HIPCHK(c, c->acc2_cnt.ensure(npix * 8));
+  }
   HIPCHK(c, hipMemsetAsync(c->acc.p, 0, npix * 48, c->stream));
   HIPCHK(c, hipMemsetAsync(c->acc_cnt.p, 0, npix * 8, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3226,6 +3255,112 @@ int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, dou
   double sum = 0.0;
   for (double v : part) sum += v;  // in block order: the result is reproducible bit for bit
   *noise = sum / (double)npix;
+  return GI_OK;
+}
+
+// ---- reprojection across views (gi.h; accum_reproject_kernel) -------------------------------
+void gi_reproject_params_default(gi_reproject_params *p) {
+  if (!p) return;
+  p->max_history = 32;
+  p->depth_tol = 0.02;
+  p->normal_min = 0.9;
+  p->albedo_tol = 0.05;
+}
+
+static double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+int gi_accum_reproject(gi_ctx *c, const gi_view *prev_view, const gi_pixel_features *prev_feat,
+                       const gi_pixel_features *cur_feat, const gi_reproject_params *pp,
+                       gi_reproject_stats *stats, double *kernel_ms) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (rc) return rc;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded (gi_read_scene)");
+  if (!prev_view || !prev_feat || !cur_feat) return fail(c, GI_ERR_ARG, "reproject: null view or planes");
+  gi_reproject_params P;
+  gi_reproject_params_default(&P);
+  if (pp) P = *pp;
+  if (P.max_history < 2) return fail(c, GI_ERR_ARG, "reproject: max_history below 2");
+  for (double t : {P.depth_tol, P.albedo_tol})
+    if (!std::isfinite(t) || t < 0.0)
+      return fail(c, GI_ERR_ARG, "reproject: tolerances must be finite and not negative");
+  if (!(P.normal_min >= 0.0 && P.normal_min <= 1.0))
+    return fail(c, GI_ERR_ARG, "reproject: normal_min outside [0, 1]");
+  DeviceScope dev(c->device);
+  const int w = c->acc_w, h = c->acc_h;
+  const size_t npix = (size_t)w * h;
+  const size_t nwaves = (size_t)reproject_waves(w, h);
+  HIPCHK(c, c->acc2.ensure(npix * 48));
+  HIPCHK(c, c->acc2_cnt.ensure(npix * 8));
+  HIPCHK(c, c->acc_part.ensure(nwaves * 16));
+  HIPCHK(c, upload(c->rp_prev, prev_feat, npix * sizeof(gi_pixel_features), c->stream));
+  HIPCHK(c, upload(c->rp_cur, cur_feat, npix * sizeof(gi_pixel_features), c->stream));
+  ReprojectArgs a;
+  memset(&a, 0, sizeof a);
+  a.W = w;
+  a.H = h;
+  a.max_history = P.max_history;
+  a.depth_tol = P.depth_tol;
+  a.nmin2 = P.normal_min * P.normal_min;
+  a.atol2 = P.albedo_tol * P.albedo_tol;
+  const DCamera cam = make_camera(c->scene, c->P);
+  for (int i = 0; i < 3; i++) {
+    a.eye1[i] = cam.eye[i];
+    a.org1[i] = cam.far_org[i];
+    a.right1[i] = cam.far_right[i];
+    a.up1[i] = cam.far_up[i];
+    a.eye0[i] = prev_view->eye[i];
+    a.right0[i] = prev_view->far_right[i];
+    a.up0[i] = prev_view->far_up[i];
+    a.G[i] = prev_view->far_org[i] - prev_view->eye[i];
+  }
+  a.GG = dot3(a.G, a.G);
+  a.RR = dot3(a.right0, a.right0);
+  a.UU = dot3(a.up0, a.up0);
+  a.acc = c->acc.as<double>();
+  a.counts = c->acc_cnt.as<int64_t>();
+  a.prev = c->rp_prev.as<float4>();
+  a.cur = c->rp_cur.as<float4>();
+  a.acc_out = c->acc2.as<double>();
+  a.counts_out = c->acc2_cnt.as<int64_t>();
+  a.partial = c->acc_part.as<int64_t>();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+      hipEventDestroy(e0);
+      return fail(c, GI_ERR_HIP, "reproject: hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, c->stream);
+  }
+  launch_accum_reproject(a, c->stream);
+  hipError_t le = hipGetLastError();
+  if (kernel_ms) (void)hipEventRecord(e1, c->stream);
+  std::vector<int64_t> part(nwaves * 2);
+  if (le == hipSuccess)
+    le = hipMemcpyAsync(part.data(), c->acc_part.p, nwaves * 16, hipMemcpyDeviceToHost, c->stream);
+  if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
+  if (kernel_ms) {
+    float ms = 0.f;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    *kernel_ms = ms;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  HIPCHK(c, le);
+  std::swap(c->acc, c->acc2);
+  std::swap(c->acc_cnt, c->acc2_cnt);
+  c->acc_uniform = false;  // every pixel under its own count from here on
+  if (stats) {
+    int64_t kept = 0, samples = 0;
+    for (size_t v = 0; v < nwaves; v++) {
+      kept += part[2 * v];
+      samples += part[2 * v + 1];
+    }
+    stats->kept_pixels = kept;
+    stats->reset_pixels = (int64_t)npix - kept;
+    stats->kept_samples = samples;
+  }
   return GI_OK;
 }
 

@@ -85,6 +85,36 @@ struct SelectArgs {
   uint8_t *mask;            // [tiles] 1 = active
 };
 
+// accum_reproject_kernel (gi.h "reprojection across views"): one thread per pixel of the current
+// frame, block 64 x 4 (a wave is 64 pixels of one row). The thread gathers its history from up to
+// four pixels of the old accumulator and writes the new record and count; a pixel without history
+// gets zeros. Wave v = block * 4 + threadIdx.y (blocks row-major over the frame) writes partial[2 v]
+// = its pixels that kept history and partial[2 v + 1] = the sum of their new counts (integers:
+// any order gives the same sums). The host precomputes what is the same for every pixel.
+constexpr int REPROJECT_BX = 64, REPROJECT_BY = 4;
+struct ReprojectArgs {
+  int32_t W, H;
+  int64_t max_history;
+  double depth_tol;
+  double nmin2;             // normal_min * normal_min
+  double atol2;             // albedo_tol * albedo_tol
+  double eye1[3], org1[3], right1[3], up1[3];  // the current view
+  double eye0[3], right0[3], up0[3];           // the previous view
+  double G[3];              // far_org0 - eye0
+  double GG, RR, UU;        // G . G, far_right0 . far_right0, far_up0 . far_up0
+  const double *acc;        // [W * H * 6] the old accumulator
+  const int64_t *counts;    // [W * H]
+  const float4 *prev;       // [W * H * 2] planes of the old frame: {normal, depth}, {albedo, coverage}
+  const float4 *cur;        // [W * H * 2] planes of the current frame
+  double *acc_out;          // [W * H * 6]
+  int64_t *counts_out;      // [W * H]
+  int64_t *partial;         // [waves * 2]
+};
+inline int64_t reproject_waves(int w, int h) {
+  return (int64_t)((w + REPROJECT_BX - 1) / REPROJECT_BX) * ((h + REPROJECT_BY - 1) / REPROJECT_BY) *
+         REPROJECT_BY;
+}
+
 // tonemap_kernel: one thread per channel value
 struct TonemapArgs {
   int64_t nval;             // W * H * 3
@@ -100,6 +130,7 @@ void launch_accum_noise(const NoiseArgs &a, hipStream_t st);
 void launch_count_stats(const CountArgs &a, hipStream_t st);
 void launch_tile_error(const TileArgs &a, hipStream_t st);
 void launch_tile_select(const SelectArgs &a, hipStream_t st);
+void launch_accum_reproject(const ReprojectArgs &a, hipStream_t st);
 void launch_tonemap(const TonemapArgs &a, hipStream_t st);
 
 }  // namespace gi

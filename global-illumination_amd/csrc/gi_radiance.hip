@@ -12,6 +12,7 @@
 //   count_stats_kernel       smallest and summed per-pixel sample count
 //   tile_error_kernel        adaptive passes: the same error per tile, one wave per tile
 //   tile_select_kernel       ... and the tile mask (thresholds, 8-neighbour dilation)
+//   accum_reproject_kernel   the accumulator carried into a new camera (tests/reproject_ref.py)
 //   tonemap_kernel           exposure, extended Reinhard curve, clamp
 #include <hip/hip_runtime.h>
 #include "gi_radiance.h"
@@ -204,6 +205,99 @@ __global__ __launch_bounds__(256) void tile_select_kernel(SelectArgs a) {
   a.mask[t] = active ? 1 : 0;
 }
 
+// The history of pixel (x, y) of the current frame, gi.h "reprojection across views" step by step.
+// A gather: the four taps of neighbouring lanes are neighbouring records of the old accumulator
+// (48 B each) and of the old planes (32 B each), so a wave reads a few contiguous runs; the old
+// buffers are only read, the new ones only written. The fp64 divisions are IEEE ones (the
+// restatement must see the same bits), which is what the kernel's time goes to beside its bytes.
+__global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void accum_reproject_kernel(ReprojectArgs a) {
+  const int bx = (a.W + REPROJECT_BX - 1) / REPROJECT_BX;  // blocks per row of blocks
+  const int x = (int)(blockIdx.x % bx) * REPROJECT_BX + threadIdx.x;
+  const int y = (int)(blockIdx.x / bx) * REPROJECT_BY + threadIdx.y;
+  const bool inside = x < a.W && y < a.H;
+  double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int64_t nn = 0;
+  if (inside) {
+    const int64_t p = (int64_t)y * a.W + x;
+    const float4 f0 = a.cur[2 * p], f1 = a.cur[2 * p + 1];
+    const double W = (double)a.W, H = (double)a.H;
+    double hs = 0.0, sm[3] = {0.0, 0.0, 0.0}, sv[3] = {0.0, 0.0, 0.0};
+    int64_t nmin = INT64_MAX;
+    if (f1.w != 0.0f) {
+      const double dx = (double)(2 * x + 1 - a.W) / W;
+      const double dy = (double)(2 * y + 1 - a.H) / H;
+      double D[3], v[3];
+      for (int k = 0; k < 3; k++) D[k] = ((a.org1[k] + a.right1[k] * dx) + a.up1[k] * dy) - a.eye1[k];
+      const double l = sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
+      const double z = (double)f0.w;
+      for (int k = 0; k < 3; k++) {
+        const double d = l == 0.0 ? D[k] : D[k] / l;  // normalize (gi_device.h)
+        v[k] = (a.eye1[k] + d * z) - a.eye0[k];
+      }
+      const double al = ((v[0] * a.G[0] + v[1] * a.G[1]) + v[2] * a.G[2]) / a.GG;
+      if (al > 0.0) {
+        const double sx = (((v[0] * a.right0[0] + v[1] * a.right0[1]) + v[2] * a.right0[2]) / a.RR) / al;
+        const double sy = (((v[0] * a.up0[0] + v[1] * a.up0[1]) + v[2] * a.up0[2]) / a.UU) / al;
+        const double u = ((sx + 1.0) * W) * 0.5 - 0.5, t = ((sy + 1.0) * H) * 0.5 - 0.5;
+        const double x0 = floor(u), y0 = floor(t);
+        const double fx = u - x0, fy = t - y0;
+        const double r = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+        const double n0 = (double)f0.x, n1 = (double)f0.y, n2 = (double)f0.z;
+        const double npp = (n0 * n0 + n1 * n1) + n2 * n2;
+        const double a0 = (double)f1.x, a1 = (double)f1.y, a2 = (double)f1.z;
+        for (int j = 0; j < 2; j++)
+          for (int i = 0; i < 2; i++) {
+            const double tx = x0 + (double)i, ty = y0 + (double)j;
+            // in doubles: a projection far outside the frame (or a NaN) never becomes an index
+            if (!(tx >= 0.0 && tx <= W - 1.0 && ty >= 0.0 && ty <= H - 1.0)) continue;
+            const double h = (i ? fx : 1.0 - fx) * (j ? fy : 1.0 - fy);
+            if (!(h >= 0.0009765625)) continue;  // 2^-10
+            const int64_t q = (int64_t)ty * a.W + (int64_t)tx;
+            const int64_t nq = a.counts[q];
+            if (nq < 2) continue;
+            const float4 g0 = a.prev[2 * q], g1 = a.prev[2 * q + 1];
+            if (!(g1.w > 0.0f)) continue;
+            if (!(fabs(r - (double)g0.w) <= a.depth_tol * r)) continue;
+            const double m0 = (double)g0.x, m1 = (double)g0.y, m2 = (double)g0.z;
+            const double c = (n0 * m0 + n1 * m1) + n2 * m2;
+            const double nqq = (m0 * m0 + m1 * m1) + m2 * m2;
+            if (!(c > 0.0 && c * c >= ((a.nmin2 * npp) * nqq))) continue;
+            const double e0 = a0 - (double)g1.x, e1 = a1 - (double)g1.y, e2 = a2 - (double)g1.z;
+            if (!((e0 * e0 + e1 * e1) + e2 * e2 <= a.atol2)) continue;
+            const double *g = a.acc + q * 6;
+            const double q1 = (double)(nq - 1);
+            hs += h;
+            for (int k = 0; k < 3; k++) {
+              sm[k] += h * g[k];
+              sv[k] += h * (g[3 + k] / q1);
+            }
+            nmin = nq < nmin ? nq : nmin;
+          }
+      }
+    }
+    if (nmin != INT64_MAX) {
+      nn = nmin < a.max_history ? nmin : a.max_history;
+      const double n1 = (double)(nn - 1);
+      for (int k = 0; k < 3; k++) {
+        o[k] = sm[k] / hs;
+        o[3 + k] = (sv[k] / hs) * n1;
+      }
+    }
+    double *g = a.acc_out + p * 6;
+    for (int k = 0; k < 6; k++) g[k] = o[k];
+    a.counts_out[p] = nn;
+  }
+  // per wave: a lane outside the frame adds nothing
+  const int kept = __popcll(__ballot(nn > 0));
+  long long s = nn;
+  for (int h = 32; h >= 1; h >>= 1) s += __shfl_down(s, h, 64);
+  if (threadIdx.x == 0) {
+    const int64_t wv = (int64_t)blockIdx.x * REPROJECT_BY + threadIdx.y;
+    a.partial[2 * wv] = kept;
+    a.partial[2 * wv + 1] = s;
+  }
+}
+
 __global__ __launch_bounds__(256) void tonemap_kernel(TonemapArgs a) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.nval) return;
@@ -236,6 +330,11 @@ void launch_tile_error(const TileArgs &a, hipStream_t st) {
 void launch_tile_select(const SelectArgs &a, hipStream_t st) {
   const int64_t nt = (int64_t)a.tiles_x * a.tiles_y;
   if (nt > 0) tile_select_kernel<<<nblk(nt, 256), 256, 0, st>>>(a);
+}
+void launch_accum_reproject(const ReprojectArgs &a, hipStream_t st) {
+  if (a.W <= 0 || a.H <= 0) return;
+  const unsigned grid = (unsigned)(reproject_waves(a.W, a.H) / REPROJECT_BY);  // row-major blocks
+  accum_reproject_kernel<<<grid, dim3(REPROJECT_BX, REPROJECT_BY), 0, st>>>(a);
 }
 void launch_tonemap(const TonemapArgs &a, hipStream_t st) {
   if (a.nval > 0) tonemap_kernel<<<nblk(a.nval, 256), 256, 0, st>>>(a);

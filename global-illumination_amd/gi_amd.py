@@ -14,6 +14,8 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
                    the noisy tiles of the accumulator (gi.h "adaptive passes")
   denoise_radiance / accum_denoise: the variance-guided denoise of a radiance frame and of
                    the accumulator (gi.h "variance-guided denoise")
+  get_view / accum_reproject: the accumulator carried into a new camera (gi.h "reprojection
+                   across views")
   render_radiance / render_rays_radiance / accum_* / tonemap / write_image_float: unclamped
                    radiance frames with their variance, accumulation over passes and the tone
                    map (no reference counterpart; gi.h "radiance frames, accumulation over
@@ -51,6 +53,7 @@ EXPORTED = [
     "gi_accum_get_counts", "gi_adaptive_params_default", "gi_accum_select", "gi_accum_add_tiles",
     "gi_accum_add_adaptive", "gi_adaptive_bench",
     "gi_vdenoise_params_default", "gi_denoise_radiance", "gi_accum_denoise",
+    "gi_get_view", "gi_reproject_params_default", "gi_accum_reproject",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
@@ -110,6 +113,24 @@ class VDenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32),
                 ("sigma_lum", C.c_double), ("sigma_depth", C.c_double),
                 ("sigma_albedo", C.c_double), ("variance_floor", C.c_double)]
+
+
+class View(C.Structure):
+    """gi_view: the pinhole frame the device renders from."""
+    _fields_ = [("eye", C.c_double * 3), ("far_org", C.c_double * 3),
+                ("far_right", C.c_double * 3), ("far_up", C.c_double * 3)]
+
+
+class ReprojectParams(C.Structure):
+    """gi_reproject_params"""
+    _fields_ = [("max_history", C.c_int64), ("depth_tol", C.c_double),
+                ("normal_min", C.c_double), ("albedo_tol", C.c_double)]
+
+
+class ReprojectStats(C.Structure):
+    """gi_reproject_stats"""
+    _fields_ = [("kept_pixels", C.c_int64), ("reset_pixels", C.c_int64),
+                ("kept_samples", C.c_int64)]
 
 
 class AdaptiveParams(C.Structure):
@@ -249,6 +270,11 @@ def lib():
                                           P(C.c_double)]
         L.gi_accum_denoise.argtypes = [C.c_void_p, C.c_void_p, P(VDenoiseParams), C.c_void_p,
                                        C.c_void_p, P(C.c_double)]
+        L.gi_get_view.argtypes = [C.c_void_p, P(View)]
+        L.gi_reproject_params_default.argtypes = [P(ReprojectParams)]
+        L.gi_reproject_params_default.restype = None
+        L.gi_accum_reproject.argtypes = [C.c_void_p, P(View), C.c_void_p, C.c_void_p,
+                                         P(ReprojectParams), P(ReprojectStats), P(C.c_double)]
         L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                  C.c_double, C.c_void_p, C.c_void_p]
         L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -291,6 +317,17 @@ def default_vdenoise_params(**kw):
     for k, v in kw.items():
         if k not in dict(VDenoiseParams._fields_):
             raise TypeError(f"unknown vdenoise parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def reproject_params(**kw):
+    """gi_reproject_params: the defaults (gi_reproject_params_default) with the given fields set."""
+    p = ReprojectParams()
+    lib().gi_reproject_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(ReprojectParams._fields_):
+            raise TypeError(f"unknown reproject parameter {k}")
         setattr(p, k, v)
     return p
 
@@ -697,6 +734,32 @@ class Renderer:
         self._check(lib().gi_accum_denoise(self._ctx, feat.ctypes.data, C.byref(p),
                                            out.ctypes.data, vlum.ctypes.data, C.byref(ms)))
         return out, vlum, ms.value
+
+    def get_view(self):
+        """The pinhole frame the device renders from under the current camera and focus_depth
+        (gi_get_view): a View; save it before set_camera to name the previous camera later."""
+        v = View()
+        self._check(lib().gi_get_view(self._ctx, C.byref(v)))
+        return v
+
+    def accum_reproject(self, prev_view, prev_feat, cur_feat, params=None, **kw):
+        """Carry the accumulator from prev_view (a View; prev_feat its frame's planes) into the
+        current camera (cur_feat: the planes of the same frame now) (gi_accum_reproject). params:
+        ReprojectParams, or the defaults with the keyword fields set. Returns (stats dict:
+        kept_pixels, reset_pixels, kept_samples; kernel_ms)."""
+        prev_feat = np.ascontiguousarray(prev_feat, dtype=FEATURE_DTYPE)
+        cur_feat = np.ascontiguousarray(cur_feat, dtype=FEATURE_DTYPE)
+        w, h = getattr(self, "_accum_size", (0, 0))
+        if w and (prev_feat.shape != (h, w) or cur_feat.shape != (h, w)):
+            raise ValueError(f"planes {prev_feat.shape}, {cur_feat.shape} do not match the "
+                             f"accumulator's {(h, w)}")
+        p = params if params is not None else reproject_params(**kw)
+        st = ReprojectStats()
+        ms = C.c_double(0.0)
+        self._check(lib().gi_accum_reproject(self._ctx, C.byref(prev_view),
+                                             prev_feat.ctypes.data, cur_feat.ctypes.data,
+                                             C.byref(p), C.byref(st), C.byref(ms)))
+        return {f: getattr(st, f) for f, _ in ReprojectStats._fields_}, ms.value
 
     def tonemap(self, radiance, exposure=1.0, white=0.0, want_float=False):
         """Exposure, extended Reinhard curve (white > 0; 0: linear) and clamp of a radiance frame

@@ -20,10 +20,18 @@
 // passes the accumulator is filtered by L levels of the variance-guided pass over its feature
 // planes (gi_camera_features + gi_accum_denoise, other parameters default) and the written image
 // is gi_tonemap of the filtered mean. -radiance FILE still receives the unfiltered mean.
+// Extension: -views FILE (one of the radiance flags; not with -denoise): FILE holds one camera per
+// line, ten numbers as in -camera (blank lines and # lines skipped). The maps are built once; view
+// k gets gi_set_camera and the pass loop above, and its image (and -radiance file) is written with
+// .%04d of k before the extension. -history H (H >= 2, only with -views): from the second view on
+// the accumulator is not emptied but carried into the new camera (gi_camera_features +
+// gi_accum_reproject with max_history = H); with -adaptive the view then goes straight to adaptive
+// passes, which refine the tiles whose history was lost.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "../../include/gi.h"
 
@@ -183,6 +191,54 @@ static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
   return nullptr;
 }
 
+// -views FILE: one camera per line, ten numbers as in -camera; blank lines and lines starting with
+// # are skipped. false with bad_line = 0 when the file cannot be opened, else on the first line
+// that is not ten finite numbers.
+static bool ReadViews(const char *path, std::vector<gi_camera> &views, int &bad_line) {
+  FILE *f = fopen(path, "r");
+  if (!f) return false;
+  char line[4096];
+  for (int ln = 1; fgets(line, sizeof line, f); ln++) {
+    const char *q = line;
+    while (*q == ' ' || *q == '\t' || *q == '\r' || *q == '\n') q++;
+    if (!*q || *q == '#') continue;
+    double v[10];
+    int n = 0;
+    bool ok = true;
+    while (ok) {
+      while (*q == ' ' || *q == '\t' || *q == '\r' || *q == '\n') q++;
+      if (!*q) break;
+      char *end = nullptr;
+      const double x = strtod(q, &end);
+      if (end == q || !(x - x == 0.0) || n == 10) ok = false;
+      else v[n++] = x;
+      q = end;
+    }
+    if (!ok || n != 10) {
+      bad_line = ln;
+      fclose(f);
+      return false;
+    }
+    gi_camera cam;
+    for (int i = 0; i < 3; i++) { cam.eye[i] = v[i]; cam.towards[i] = v[3 + i]; cam.up[i] = v[6 + i]; }
+    cam.xfov = v[9];
+    views.push_back(cam);
+  }
+  fclose(f);
+  return true;
+}
+
+// path with ".%04d" of k before its extension (appended when it has none)
+static std::string NumberedPath(const char *path, int k) {
+  std::string p(path);
+  char num[16];
+  snprintf(num, sizeof num, ".%04d", k);
+  const size_t slash = p.find_last_of('/');
+  const size_t dot = p.find_last_of('.');
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return p + num;
+  return p.substr(0, dot) + num + p.substr(dot);
+}
+
 int main(int argc, char **argv) {
   gi_camera cam;
   bool have_cam = false;
@@ -206,6 +262,43 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (vdenoise_levels) rad.any = true;
+  // -views FILE / -history H: one of the radiance flags; malformed ones exit -1
+  const char *views_file = nullptr, *history_text = nullptr;
+  std::vector<gi_camera> views;
+  long history = 0;  // 0: every view starts from an empty accumulator
+  if (!TakeValue(argc, argv, "-views", &views_file)) {
+    fprintf(stderr, "Invalid program argument: -views\n");
+    return -1;
+  }
+  if (!TakeValue(argc, argv, "-history", &history_text)) {
+    fprintf(stderr, "Invalid program argument: -history\n");
+    return -1;
+  }
+  if (history_text) {
+    char *end = nullptr;
+    history = strtol(history_text, &end, 10);
+    if (end == history_text || *end || history < 2 || !views_file) {
+      fprintf(stderr, "Invalid program argument: -history\n");
+      return -1;
+    }
+  }
+  if (views_file) {
+    if (denoise_levels) {
+      fprintf(stderr, "Invalid program argument: -views (not with -denoise)\n");
+      return -1;
+    }
+    int bad_line = 0;
+    if (!ReadViews(views_file, views, bad_line)) {
+      if (bad_line) fprintf(stderr, "Unable to read views file %s: line %d is not ten numbers\n", views_file, bad_line);
+      else fprintf(stderr, "Unable to open views file %s\n", views_file);
+      return -1;
+    }
+    if (views.empty()) {
+      fprintf(stderr, "Unable to read views file %s: no camera in it\n", views_file);
+      return -1;
+    }
+    rad.any = true;
+  }
   gi_params P;
   gi_params_default(&P);
   const char *scene = nullptr, *out = nullptr, *err = nullptr;
@@ -239,7 +332,7 @@ int main(int argc, char **argv) {
     if (ds.count == 0) ds.count = 1;
   }
   if (rad.any && ds.count > 1) {
-    fprintf(stderr, "-passes, -noise, -exposure, -white, -radiance and -vdenoise render on one device: not with -gpus %d\n",
+    fprintf(stderr, "-passes, -noise, -exposure, -white, -radiance, -vdenoise and -views render on one device: not with -gpus %d\n",
             ds.count);
     return -1;
   }
@@ -293,143 +386,193 @@ int main(int argc, char **argv) {
       fflush(stdout);
     }
   }
-  std::vector<uint8_t> rgb((size_t)w * h * 3);
-  gi_render_stats rs;
-  if (P.verbose) printf("Rendering image ...\n");
-  std::vector<float> rgbf(denoise_levels || rad.any ? (size_t)w * h * 3 : 0);
-  std::vector<float> mean(rad.any ? (size_t)w * h * 3 : 0);
-  int passes_done = 0;
-  long long acc_n = 0, acc_total = 0, acc_max = 0;
-  double acc_noise = 0.0, vdenoise_ms = 0.0;
-  if (rad.any) {
-    // passes under seed, seed + 1, ... from the same maps, folded into the accumulator; the
-    // written image is the tone-mapped unclamped mean
-    memset(&rs, 0, sizeof rs);
-    bool ok = gi_accum_reset(ctx, w, h) == GI_OK;
-    gi_adaptive_params ap;
-    gi_adaptive_params_default(&ap);
-    ap.tile_px = rad.adaptive_tile ? rad.adaptive_tile : ap.tile_px;
-    ap.threshold = rad.noise;
-    int64_t least = 0;  // the smallest per-pixel count so far
-    for (int i = 0; ok && i < rad.passes; i++) {
-      gi_params Pi = P;
-      Pi.seed = P.seed + (uint64_t)i;
-      gi_render_stats ps;
-      prog.last[0] = -1;
-      ok = gi_set_params(ctx, &Pi) == GI_OK;
-      if (ok && rad.adaptive_tile && least >= ap.min_samples) {
-        int64_t active = 0;
-        ok = gi_accum_add_adaptive(ctx, aa, &ap, nullptr, &active, &ps) == GI_OK;
-        if (ok && active == 0) break;  // every tile is at the threshold: nothing was rendered
-      } else if (ok) {
-        ok = gi_accum_add_image(ctx, aa, &ps) == GI_OK;
-      }
-      if (!ok) break;
-      passes_done++;
-      rs.render_s += ps.render_s;
-      rs.screen_rays += ps.screen_rays; rs.shadow_rays += ps.shadow_rays;
-      rs.monte_carlo_rays += ps.monte_carlo_rays; rs.transmissive_samples += ps.transmissive_samples;
-      rs.specular_samples += ps.specular_samples; rs.indirect_samples += ps.indirect_samples;
-      rs.caustic_samples += ps.caustic_samples;
-      if (rad.adaptive_tile) {
-        ok = gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
-      } else if (rad.have_noise) {  // defined from two samples per pixel on
-        int64_t n = 0;
-        ok = gi_accum_get(ctx, nullptr, nullptr, &n, &acc_noise) == GI_OK;
-        if (ok && n >= 2 && acc_noise <= rad.noise) break;
-      }
+  const int nviews = views.empty() ? 1 : (int)views.size();
+  std::vector<gi_pixel_features> prev_feat, cur_feat;  // -history: the planes of the last two views
+  gi_view prev_view;
+  memset(&prev_view, 0, sizeof prev_view);
+  for (int k = 0; k < nviews; k++) {
+    const std::string out_k = views.empty() ? std::string(out) : NumberedPath(out, k);
+    const std::string rad_k = !rad.file ? std::string() : (views.empty() ? std::string(rad.file) : NumberedPath(rad.file, k));
+    if (!views.empty() && gi_set_camera(ctx, &views[k]) != GI_OK) {
+      fprintf(stderr, "%s\n", gi_last_error(ctx));
+      gi_destroy(ctx);
+      return -1;
     }
-    if (ok && rad.adaptive_tile) {
-      std::vector<int64_t> counts((size_t)w * h);
-      int64_t total = 0;
-      ok = gi_accum_get_counts(ctx, counts.data(), &total) == GI_OK;
-      acc_total = total;
-      for (int64_t v : counts) acc_max = v > acc_max ? v : acc_max;
+    std::vector<uint8_t> rgb((size_t)w * h * 3);
+    gi_render_stats rs;
+    if (P.verbose) printf("Rendering image ...\n");
+    std::vector<float> rgbf(denoise_levels || rad.any ? (size_t)w * h * 3 : 0);
+    std::vector<float> mean(rad.any ? (size_t)w * h * 3 : 0);
+    int passes_done = 0;
+    long long acc_n = 0, acc_total = 0, acc_max = 0, primary_samples = 0;
+    double acc_noise = 0.0, vdenoise_ms = 0.0;
+    bool carried = false;  // -history: this view starts from the previous view's accumulator
+    gi_reproject_stats rps;
+    memset(&rps, 0, sizeof rps);
+    if (rad.any) {
+      // passes under seed, seed + 1, ... from the same maps, folded into the accumulator; the
+      // written image is the tone-mapped unclamped mean
+      memset(&rs, 0, sizeof rs);
+      bool ok = true;
+      int64_t least = 0;  // the smallest per-pixel count so far
+      if (history) {
+        // the new view's planes; the previous view's planes and pinhole frame are kept from the step
+        // before, and with them the accumulator is carried into this camera instead of emptied
+        cur_feat.resize((size_t)w * h);
+        ok = gi_camera_features(ctx, aa, w, h, cur_feat.data()) == GI_OK;
+        if (ok && k >= 1) {
+          gi_reproject_params rp;
+          gi_reproject_params_default(&rp);
+          rp.max_history = history;
+          ok = gi_accum_reproject(ctx, &prev_view, prev_feat.data(), cur_feat.data(), &rp, &rps, nullptr) == GI_OK &&
+               gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
+          carried = ok;
+        }
+      }
+      if (ok && !carried) ok = gi_accum_reset(ctx, w, h) == GI_OK;
+      gi_adaptive_params ap;
+      gi_adaptive_params_default(&ap);
+      ap.tile_px = rad.adaptive_tile ? rad.adaptive_tile : ap.tile_px;
+      ap.threshold = rad.noise;
+      for (int i = 0; ok && i < rad.passes; i++) {
+        gi_params Pi = P;
+        Pi.seed = P.seed + (uint64_t)i;
+        gi_render_stats ps;
+        prog.last[0] = -1;
+        ok = gi_set_params(ctx, &Pi) == GI_OK;
+        // a carried accumulator goes straight to adaptive passes: the selection's n_min < min_samples
+        // rule makes the tiles whose history was lost core
+        if (ok && rad.adaptive_tile && (carried || least >= ap.min_samples)) {
+          int64_t active = 0;
+          ok = gi_accum_add_adaptive(ctx, aa, &ap, nullptr, &active, &ps) == GI_OK;
+          if (ok && active == 0) break;  // every tile is at the threshold: nothing was rendered
+          primary_samples += (long long)active << (2 * aa);
+        } else if (ok) {
+          ok = gi_accum_add_image(ctx, aa, &ps) == GI_OK;
+          primary_samples += ((long long)w * h) << (2 * aa);
+        }
+        if (!ok) break;
+        passes_done++;
+        rs.render_s += ps.render_s;
+        rs.screen_rays += ps.screen_rays; rs.shadow_rays += ps.shadow_rays;
+        rs.monte_carlo_rays += ps.monte_carlo_rays; rs.transmissive_samples += ps.transmissive_samples;
+        rs.specular_samples += ps.specular_samples; rs.indirect_samples += ps.indirect_samples;
+        rs.caustic_samples += ps.caustic_samples;
+        if (rad.adaptive_tile) {
+          ok = gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
+        } else if (rad.have_noise) {  // defined from two samples per pixel on
+          int64_t n = 0;
+          ok = gi_accum_get(ctx, nullptr, nullptr, &n, &acc_noise) == GI_OK;
+          if (ok && n >= 2 && acc_noise <= rad.noise) break;
+        }
+      }
+      if (ok && rad.adaptive_tile) {
+        std::vector<int64_t> counts((size_t)w * h);
+        int64_t total = 0;
+        ok = gi_accum_get_counts(ctx, counts.data(), &total) == GI_OK;
+        acc_total = total;
+        for (int64_t v : counts) acc_max = v > acc_max ? v : acc_max;
+      }
+      int64_t n = 0;
+      ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK;
+      std::vector<float> filtered;  // -vdenoise: the written image is the tone-mapped filtered mean
+      if (ok && vdenoise_levels) {
+        std::vector<gi_pixel_features> feat;
+        if (!history) {
+          feat.resize((size_t)w * h);
+          ok = gi_camera_features(ctx, aa, w, h, feat.data()) == GI_OK;
+        }
+        gi_vdenoise_params vp;
+        gi_vdenoise_params_default(&vp);
+        vp.levels = vdenoise_levels;
+        filtered.resize((size_t)w * h * 3);
+        ok = ok && gi_accum_denoise(ctx, history ? cur_feat.data() : feat.data(), &vp, filtered.data(), nullptr,
+                                    &vdenoise_ms) == GI_OK;
+      }
+      ok = ok && gi_tonemap(ctx, w, h, vdenoise_levels ? filtered.data() : mean.data(), rad.exposure,
+                            rad.white, rgbf.data(), rgb.data()) == GI_OK;
+      acc_n = n;
+      gi_set_params(ctx, &P);
+      if (ok && history) {
+        ok = gi_get_view(ctx, &prev_view) == GI_OK;
+        prev_feat.swap(cur_feat);
+      }
+      if (!ok) {
+        fprintf(stderr, "%s\n", gi_last_error(ctx));
+        gi_destroy(ctx);
+        return -1;
+      }
+    } else if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
+      fprintf(stderr, "%s\n", gi_last_error(ctx));
+      gi_destroy(ctx);
+      return -1;
     }
-    int64_t n = 0;
-    ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK;
-    std::vector<float> filtered;  // -vdenoise: the written image is the tone-mapped filtered mean
-    if (ok && vdenoise_levels) {
+    double denoise_ms = 0.0;
+    if (denoise_levels) {  // the written image is the filtered frame
       std::vector<gi_pixel_features> feat((size_t)w * h);
-      gi_vdenoise_params vp;
-      gi_vdenoise_params_default(&vp);
-      vp.levels = vdenoise_levels;
-      filtered.resize((size_t)w * h * 3);
-      ok = gi_camera_features(ctx, aa, w, h, feat.data()) == GI_OK &&
-           gi_accum_denoise(ctx, feat.data(), &vp, filtered.data(), nullptr, &vdenoise_ms) == GI_OK;
+      gi_denoise_params dp;
+      gi_denoise_params_default(&dp);
+      dp.levels = denoise_levels;
+      if (gi_camera_features(ctx, aa, w, h, feat.data()) != GI_OK ||
+          gi_denoise(ctx, w, h, rgbf.data(), feat.data(), &dp, nullptr, rgb.data(), &denoise_ms) != GI_OK) {
+        fprintf(stderr, "%s\n", gi_last_error(ctx));
+        gi_destroy(ctx);
+        return -1;
+      }
     }
-    ok = ok && gi_tonemap(ctx, w, h, vdenoise_levels ? filtered.data() : mean.data(), rad.exposure,
-                          rad.white, rgbf.data(), rgb.data()) == GI_OK;
-    acc_n = n;
-    gi_set_params(ctx, &P);
-    if (!ok) {
-      fprintf(stderr, "%s\n", gi_last_error(ctx));
-      gi_destroy(ctx);
+    PrintProgress(1.0, PROGRESS_BAR_WIDTH);  // render.cpp:201-202
+    printf("\n");
+    fflush(stdout);
+    if (P.verbose) {
+      unsigned long long total = rs.screen_rays;
+      printf("Rendered image ...\n");
+      printf("  Time = %.2f seconds\n", rs.render_s);
+      printf("  # Screen Rays = %llu\n", (unsigned long long)rs.screen_rays);
+      if (P.shadows) { printf("  # Shadow Rays = %llu\n", (unsigned long long)rs.shadow_rays); total += rs.shadow_rays; }
+      if (P.monte_carlo) { printf("  # Monte Carlo Rays = %llu\n", (unsigned long long)rs.monte_carlo_rays); total += rs.monte_carlo_rays; }
+      if (P.transmissive_illum) { printf("  # Transmissive Samples = %llu\n", (unsigned long long)rs.transmissive_samples); total += rs.transmissive_samples; }
+      if (P.specular_illum) { printf("  # Specular Samples = %llu\n", (unsigned long long)rs.specular_samples); total += rs.specular_samples; }
+      if (P.indirect_illum) { printf("  # Indirect Samples = %llu\n", (unsigned long long)rs.indirect_samples); total += rs.indirect_samples; }
+      if (P.caustic_illum) { printf("  # Caustic Samples = %llu\n", (unsigned long long)rs.caustic_samples); total += rs.caustic_samples; }
+      printf("Total Rays: %llu\n", total);
+      if (!views.empty())
+        printf("View %d of %d: %lld primary samples rendered\n", k, nviews, primary_samples);
+      if (carried)
+        printf("Reprojected history: %lld pixels kept, %lld pixels reset, %lld samples kept\n",
+               (long long)rps.kept_pixels, (long long)rps.reset_pixels, (long long)rps.kept_samples);
+      if (rad.adaptive_tile)
+        printf("Accumulated image: %d passes, %lld samples, %lld to %lld per pixel, noise = %.6g\n",
+               passes_done, acc_total, acc_n, acc_max, acc_noise);
+      else if (rad.any)
+        printf("Accumulated image: %d passes, N = %lld samples per pixel, noise = %.6g\n", passes_done,
+               acc_n, acc_noise);
+      if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);
+      if (vdenoise_levels)
+        printf("Variance-guided denoise: %d levels, %.3f ms\n", vdenoise_levels, vdenoise_ms);
+      fflush(stdout);
+    }
+    if (k == nviews - 1) gi_destroy(ctx);
+    auto tw = std::chrono::steady_clock::now();
+    if (gi_write_image(out_k.c_str(), w, h, rgb.data()) != GI_OK) {
+      const char *ext = strrchr(out, '.');
+      if (ext && !strncmp(ext, ".tif", 4)) fprintf(stderr, "TIFF not supported\n");  // R2Image.cpp:1300
+      else fprintf(stderr, "Unable to write image %s\n", out_k.c_str());
+      if (k < nviews - 1) gi_destroy(ctx);
       return -1;
     }
-  } else if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
-    fprintf(stderr, "%s\n", gi_last_error(ctx));
-    gi_destroy(ctx);
-    return -1;
-  }
-  double denoise_ms = 0.0;
-  if (denoise_levels) {  // the written image is the filtered frame
-    std::vector<gi_pixel_features> feat((size_t)w * h);
-    gi_denoise_params dp;
-    gi_denoise_params_default(&dp);
-    dp.levels = denoise_levels;
-    if (gi_camera_features(ctx, aa, w, h, feat.data()) != GI_OK ||
-        gi_denoise(ctx, w, h, rgbf.data(), feat.data(), &dp, nullptr, rgb.data(), &denoise_ms) != GI_OK) {
-      fprintf(stderr, "%s\n", gi_last_error(ctx));
-      gi_destroy(ctx);
+    if (rad.file && gi_write_image_float(rad_k.c_str(), w, h, mean.data()) != GI_OK) {
+      fprintf(stderr, "Unable to write image %s\n", rad_k.c_str());
+      if (k < nviews - 1) gi_destroy(ctx);
       return -1;
     }
-  }
-  PrintProgress(1.0, PROGRESS_BAR_WIDTH);  // render.cpp:201-202
-  printf("\n");
-  fflush(stdout);
-  if (P.verbose) {
-    unsigned long long total = rs.screen_rays;
-    printf("Rendered image ...\n");
-    printf("  Time = %.2f seconds\n", rs.render_s);
-    printf("  # Screen Rays = %llu\n", (unsigned long long)rs.screen_rays);
-    if (P.shadows) { printf("  # Shadow Rays = %llu\n", (unsigned long long)rs.shadow_rays); total += rs.shadow_rays; }
-    if (P.monte_carlo) { printf("  # Monte Carlo Rays = %llu\n", (unsigned long long)rs.monte_carlo_rays); total += rs.monte_carlo_rays; }
-    if (P.transmissive_illum) { printf("  # Transmissive Samples = %llu\n", (unsigned long long)rs.transmissive_samples); total += rs.transmissive_samples; }
-    if (P.specular_illum) { printf("  # Specular Samples = %llu\n", (unsigned long long)rs.specular_samples); total += rs.specular_samples; }
-    if (P.indirect_illum) { printf("  # Indirect Samples = %llu\n", (unsigned long long)rs.indirect_samples); total += rs.indirect_samples; }
-    if (P.caustic_illum) { printf("  # Caustic Samples = %llu\n", (unsigned long long)rs.caustic_samples); total += rs.caustic_samples; }
-    printf("Total Rays: %llu\n", total);
-    if (rad.adaptive_tile)
-      printf("Accumulated image: %d passes, %lld samples, %lld to %lld per pixel, noise = %.6g\n",
-             passes_done, acc_total, acc_n, acc_max, acc_noise);
-    else if (rad.any)
-      printf("Accumulated image: %d passes, N = %lld samples per pixel, noise = %.6g\n", passes_done,
-             acc_n, acc_noise);
-    if (denoise_levels) printf("Denoised image: %d levels, %.3f ms\n", denoise_levels, denoise_ms);
-    if (vdenoise_levels)
-      printf("Variance-guided denoise: %d levels, %.3f ms\n", vdenoise_levels, vdenoise_ms);
-    fflush(stdout);
-  }
-  gi_destroy(ctx);
-  auto tw = std::chrono::steady_clock::now();
-  if (gi_write_image(out, w, h, rgb.data()) != GI_OK) {
-    const char *ext = strrchr(out, '.');
-    if (ext && !strncmp(ext, ".tif", 4)) fprintf(stderr, "TIFF not supported\n");  // R2Image.cpp:1300
-    else fprintf(stderr, "Unable to write image %s\n", out);
-    return -1;
-  }
-  if (rad.file && gi_write_image_float(rad.file, w, h, mean.data()) != GI_OK) {
-    fprintf(stderr, "Unable to write image %s\n", rad.file);
-    return -1;
-  }
-  if (P.verbose) {
-    printf("Wrote image to %s ...\n", out);
-    printf("  Time = %.2f seconds\n",
-           std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count());
-    printf("  Width = %d\n", w);
-    printf("  Height = %d\n", h);
-    fflush(stdout);
-  }
+    if (P.verbose) {
+      printf("Wrote image to %s ...\n", out_k.c_str());
+      printf("  Time = %.2f seconds\n",
+             std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count());
+      printf("  Width = %d\n", w);
+      printf("  Height = %d\n", h);
+      fflush(stdout);
+    }
+  }  // views
   return 0;
 }

@@ -489,6 +489,72 @@ int gi_denoise_radiance(gi_ctx *ctx, int width, int height, const float *mean,
 int gi_accum_denoise(gi_ctx *ctx, const gi_pixel_features *feat, const gi_vdenoise_params *p,
                      float *out_mean, float *out_variance_lum, double *kernel_ms);
 
+/* ---- reprojection across views: the accumulator carried into a new camera ------------------- */
+/* The pinhole frame the device renders from: the four vectors the host puts into the render's
+ * camera block (render.cpp:67-77) for the current camera and the current focus_depth, with the
+ * same bits: far_org = eye + towards * focus_depth, far_right = right * tan(xfov) * focus_depth,
+ * far_up = up * tan(yfov) * focus_depth over the camera's triad. The ray through (dx, dy) in
+ * [-1, 1]^2 is normalize(((far_org + far_right * dx) + far_up * dy) - eye). A caller saves the view
+ * before gi_set_camera to name the previous camera later. GI_ERR_STATE before a scene is read.
+ * No reference counterpart. */
+typedef struct gi_view { double eye[3], far_org[3], far_right[3], far_up[3]; } gi_view;
+int gi_get_view(const gi_ctx *ctx, gi_view *out);
+
+/* gi_accum_reproject. The accumulator holds W x H pixels seen from prev_view, prev_feat holds the
+ * planes of that frame and cur_feat those of the same W x H frame under the context's current
+ * camera. Afterwards the accumulator holds, at every pixel of the current frame, the history found
+ * for it: mu, A and n_p; a pixel with no history has all three zero, exactly as after
+ * gi_accum_reset, and later gi_accum_add_image / gi_accum_add_tiles / gi_accum_add_adaptive fold
+ * onto it under each pixel's own count. (Lambertian radiance does not depend on the view: the
+ * samples paid for in one view serve the next.) tests/reproject_ref.py restates the definition and
+ * the device equals it bit for bit. No reference counterpart.
+ *
+ * fp64 on the given values (float32 plane values are widened once), one IEEE operation per step in
+ * the order written, only + - * / sqrt floor and comparisons; sums and dot products run left to
+ * right over x, y, z or r, g, b; len(a) = sqrt(a . a). For pixel p = (x, y) of the current frame,
+ * subscript 1 for gi_get_view now and 0 for prev_view, planes n (normal), z (depth), a (albedo):
+ *  1. coverage_p = 0: no history.
+ *  2. dx = (2x + 1 - W) / W, dy = (2y + 1 - H) / H (the pixel centre),
+ *     D = ((far_org1 + far_right1 * dx) + far_up1 * dy) - eye1, d = D / len(D) (D when len is 0).
+ *  3. X = eye1 + d * z_p.
+ *  4. v = X - eye0, G = far_org0 - eye0, a = (v . G) / (G . G); a <= 0: no history.
+ *     sx = ((v . far_right0) / (far_right0 . far_right0)) / a, sy likewise with far_up0;
+ *     u = ((sx + 1) * W) * 0.5 - 0.5, t = ((sy + 1) * H) * 0.5 - 0.5;
+ *     x0 = floor(u), fx = u - x0, y0 = floor(t), fy = t - y0; r = len(v).
+ *  5. taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner, weight
+ *     h = (i ? fx : 1 - fx) * (j ? fy : 1 - fy). A tap counts when it lies inside the image,
+ *     h >= 2^-10, n_q >= 2, the previous coverage_q > 0, |r - z_q| <= depth_tol * r,
+ *     c = n_p . n_q > 0 and c * c >= ((normal_min * normal_min) * (n_p . n_p)) * (n_q . n_q), and
+ *     |a_p - a_q|^2 <= albedo_tol * albedo_tol.
+ *  6. no tap counts: no history.
+ *  7. otherwise, sums from 0 over the counting taps in tap order: hs = sum h; per channel
+ *     mu' = (sum h * mu_q) / hs, s2 = (sum h * (A_q / (n_q - 1))) / hs;
+ *     n' = min(min_q n_q, max_history), A' = s2 * (n' - 1).
+ * The carried per-sample variance is the taps' weighted mean, not sum h^2 (interpolated samples
+ * are correlated: the conservative choice); the count is the smallest tap count, so a pixel never
+ * claims more history than its least-sampled source; the 2^-10 floor keeps a neighbour at weight
+ * ~1e-16 from dragging n' down when the camera did not move.
+ * stats (optional): kept_pixels + reset_pixels = W * H, kept_samples = sum n'. kernel_ms
+ * (optional): HIP-event time of the kernel. GI_ERR_UNSUPPORTED on a device set; GI_ERR_STATE before
+ * gi_accum_reset or before a scene is read; GI_ERR_ARG for a null view or planes, max_history < 2,
+ * a tolerance that is negative or not finite, or normal_min outside [0, 1]. A refused call leaves
+ * the accumulator as it was.
+ * Accepted limits: view-dependent radiance (specular lobes, what a mirror or glass shows) is
+ * carried as if it were diffuse, bounded by max_history; depth is the mean distance over a pixel's
+ * samples and the point is placed on the centre ray; camera frames only; one device. */
+typedef struct gi_reproject_params {
+  int64_t max_history;   /* >= 2: cap of a carried count;              default 32   */
+  double depth_tol;      /* relative, finite, >= 0;                    default 0.02 */
+  double normal_min;     /* cosine in [0, 1];                          default 0.9  */
+  double albedo_tol;     /* finite, >= 0;                              default 0.05 */
+} gi_reproject_params;
+void gi_reproject_params_default(gi_reproject_params *p);
+typedef struct gi_reproject_stats { int64_t kept_pixels, reset_pixels, kept_samples; } gi_reproject_stats;
+int gi_accum_reproject(gi_ctx *ctx, const gi_view *prev_view,
+                       const gi_pixel_features *prev_feat, const gi_pixel_features *cur_feat,
+                       const gi_reproject_params *p /* NULL: defaults */,
+                       gi_reproject_stats *stats /* optional */, double *kernel_ms /* optional */);
+
 /* Tone map of a radiance frame (W*H*3 floats), per channel in fp64: x = exposure * c;
  * y = x * (1 + x / (white * white)) / (1 + x) when white > 0 (extended Reinhard: `white` maps to
  * 1), y = x when white == 0; clamped to [0, 1], rounded to float32. Linear output, as the
