@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gi_dbuf.h"
 
 namespace gi {
 // emission-ordered photon record as gi_photon (include/gi.h) / gi_photon_dev: 20 bytes
@@ -14,17 +15,14 @@ struct KdPhoton {
 static_assert(sizeof(KdPhoton) == 20, "photon record is 20 bytes");
 
 struct KdBuildScratch {
-  uint32_t *perm0 = nullptr, *perm1 = nullptr, *box = nullptr;
-  uint64_t *key0 = nullptr, *key1 = nullptr;
-  int32_t *axis = nullptr;
-  void *tmp = nullptr;
-  size_t perm_cap0 = 0, perm_cap1 = 0, key_cap0 = 0, key_cap1 = 0, box_cap = 0, axis_cap = 0,
-         tmp_cap = 0;
+  DBuf perm0, perm1, box;  // uint32_t
+  DBuf key0, key1;         // uint64_t
+  DBuf axis;               // int32_t
+  DBuf tmp;
   hipError_t grow(int64_t n, int64_t L);
-  void release();
 };
 
-// Builds the map's implicit kd tree (leaves of <= leaf_size photons; gi_host.cpp HostMap
+// Builds the map's implicit kd tree (leaves of <= leaf_size photons; gi_ctx.h HostMap
 // layout) from n emission-ordered photons on the device: pos4 (16 B per photon), rgbe and nodes
 // (16 * L floats) in kd order, perm_out (host memory, may be null) = kd order -> emission index.
 // Asynchronous on st (perm_out is valid after the stream synchronises).

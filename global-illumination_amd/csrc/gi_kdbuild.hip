@@ -2,7 +2,7 @@
 //
 // The reference inserts photons into an R3Kdtree (R3Kdtree.cpp:1552-1671: recursive median
 // split of each node's point range along its box's longest axis, random-pivot quickselect). The
-// device map keeps the same kind of tree in the layout the k-NN kernels read (gi_host.cpp
+// device map keeps the same kind of tree in the layout the k-NN kernels read (gi_ctx.h
 // HostMap, KdView): an implicit complete tree over L = 2^levels leaves, leaf l owning kd-order
 // positions [l*n/L, (l+1)*n/L), node v's range the union of its leaves'. Node v splits its range
 // at the median position along the longest axis of its photons' tight box; its record is
@@ -184,22 +184,23 @@ hipError_t kd_build_device(const KdPhoton *ph, int64_t n, int leaf_size, KdBuild
     return e;
   }
   if ((e = s.grow(n, L)) != hipSuccess) return e;
-  uint32_t *pa = s.perm0, *pb = s.perm1;
-  uint64_t *ka = s.key0, *kb = s.key1;
+  uint32_t *pa = s.perm0.as<uint32_t>(), *pb = s.perm1.as<uint32_t>(), *box = s.box.as<uint32_t>();
+  uint64_t *ka = s.key0.as<uint64_t>(), *kb = s.key1.as<uint64_t>();
+  int32_t *axis = s.axis.as<int32_t>();
   kd_iota_kernel<<<blocks(n, 256), 256, 0, st>>>(pa, n);
   for (int d = 0; d <= levels; d++) {
     const int64_t nn = (int64_t)1 << d;
-    kd_box_init_kernel<<<blocks(6 * nn, 256), 256, 0, st>>>(s.box, nn);
-    kd_box_kernel<<<blocks(n, 256), 256, 0, st>>>(ph, pa, n, L, levels, d, s.box);
-    kd_node_kernel<<<blocks(nn, 256), 256, 0, st>>>(s.box, n, L, levels, d, nodes, s.axis);
+    kd_box_init_kernel<<<blocks(6 * nn, 256), 256, 0, st>>>(box, nn);
+    kd_box_kernel<<<blocks(n, 256), 256, 0, st>>>(ph, pa, n, L, levels, d, box);
+    kd_node_kernel<<<blocks(nn, 256), 256, 0, st>>>(box, n, L, levels, d, nodes, axis);
     if (d == levels) break;
     const int hb = std::min(12, 32 - d);  // hash bits below the coordinate
-    kd_key_kernel<<<blocks(n, 256), 256, 0, st>>>(ph, pa, n, L, levels, d, hb, s.axis, ka);
-    size_t tb = s.tmp_cap;
-    e = hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, ka, kb, pa, pb, (int)n, 0, 32 + d + hb, st);
+    kd_key_kernel<<<blocks(n, 256), 256, 0, st>>>(ph, pa, n, L, levels, d, hb, axis, ka);
+    size_t tb = s.tmp.cap;
+    e = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tb, ka, kb, pa, pb, (int)n, 0, 32 + d + hb, st);
     if (e != hipSuccess) return e;
     std::swap(pa, pb);
-    kd_split_kernel<<<blocks(nn, 256), 256, 0, st>>>(ph, pa, n, L, d, nodes, s.axis);
+    kd_split_kernel<<<blocks(nn, 256), 256, 0, st>>>(ph, pa, n, L, d, nodes, axis);
   }
   kd_finish_kernel<<<blocks(n, 256), 256, 0, st>>>(ph, pa, n, reinterpret_cast<float4 *>(pos4), rgbe);
   if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -207,34 +208,20 @@ hipError_t kd_build_device(const KdPhoton *ph, int64_t n, int leaf_size, KdBuild
   return e;
 }
 
+// The first allocation is exact, a re-growth (a larger map after a smaller one) gets DBuf's headroom.
 hipError_t KdBuildScratch::grow(int64_t n, int64_t L) {
-  auto g = [](void **p, size_t &cap, size_t bytes) -> hipError_t {
-    if (bytes <= cap && *p) return hipSuccess;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    hipError_t r = hipMalloc(p, bytes);
-    if (r == hipSuccess) cap = bytes;
-    return r;
-  };
   hipError_t e;
-  if ((e = g((void **)&perm0, perm_cap0, (size_t)n * 4)) != hipSuccess) return e;
-  if ((e = g((void **)&perm1, perm_cap1, (size_t)n * 4)) != hipSuccess) return e;
-  if ((e = g((void **)&key0, key_cap0, (size_t)n * 8)) != hipSuccess) return e;
-  if ((e = g((void **)&key1, key_cap1, (size_t)n * 8)) != hipSuccess) return e;
-  if ((e = g((void **)&box, box_cap, (size_t)6 * 4 * L)) != hipSuccess) return e;
-  if ((e = g((void **)&axis, axis_cap, (size_t)4 * L)) != hipSuccess) return e;
+  if ((e = perm0.ensure((size_t)n * 4)) != hipSuccess) return e;
+  if ((e = perm1.ensure((size_t)n * 4)) != hipSuccess) return e;
+  if ((e = key0.ensure((size_t)n * 8)) != hipSuccess) return e;
+  if ((e = key1.ensure((size_t)n * 8)) != hipSuccess) return e;
+  if ((e = box.ensure((size_t)6 * 4 * L)) != hipSuccess) return e;
+  if ((e = axis.ensure((size_t)4 * L)) != hipSuccess) return e;
   size_t tb = 0;
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key0, key1, perm0, perm1, (int)n, 0, 64);
+  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key0.as<uint64_t>(), key1.as<uint64_t>(),
+                                         perm0.as<uint32_t>(), perm1.as<uint32_t>(), (int)n, 0, 64);
   if (e != hipSuccess) return e;
-  return g(&tmp, tmp_cap, tb + 256);
-}
-
-void KdBuildScratch::release() {
-  void *ps[] = {perm0, perm1, key0, key1, box, axis, tmp};
-  for (void *p : ps)
-    if (p) hipFree(p);
-  *this = KdBuildScratch();
+  return tmp.ensure(tb + 256);
 }
 
 }  // namespace gi

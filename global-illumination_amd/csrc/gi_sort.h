@@ -2,14 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gi_dbuf.h"
 
 namespace gi {
 struct SortScratch {
-  void *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr, *tmp = nullptr;
-  size_t k0_cap = 0, k1_cap = 0, v0_cap = 0, v1_cap = 0, tmp_cap = 0;
-  // curve_order_rows: the row masks and their counts / offsets
-  void *rows = nullptr, *cnt = nullptr;
-  size_t rows_cap = 0, cnt_cap = 0;
+  DBuf k0, k1, v0, v1, tmp;
+  DBuf rows, cnt;  // curve_order_rows: the row masks and their counts / offsets
 };
 // returns a device permutation (sorted position -> query index) valid until the next call
 hipError_t morton_order(const float4 *q, int64_t n, const float bmin[3], const float bmax[3],
@@ -35,7 +33,6 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
                             uint32_t qbase, int64_t nq, const float bmin[3], const float bmax[3],
                             SortScratch &s, uint32_t **perm_out, int64_t *nvalid, hipStream_t st,
                             bool surf = false);
-void sort_scratch_release(SortScratch &s);
 // key parameters: the 3-D curve's 10-bit cells (origin o, scale s per axis, cmax), or, with surf,
 // the surface key's square 11-bit cells (siso) and 32 depth slabs per axis (sdep)
 struct KeyGeom {
@@ -45,11 +42,9 @@ struct KeyGeom {
 };
 
 struct KeySortScratch {
-  void *k1 = nullptr, *v0 = nullptr, *v1 = nullptr, *tmp = nullptr;
-  size_t k1_cap = 0, v0_cap = 0, v1_cap = 0, tmp_cap = 0;
+  DBuf k1, v0, v1, tmp;
 };
 // stable order of 64-bit keys: sorted keys + the original slot of each
 hipError_t key_order(const uint64_t *keys, int64_t n, int key_bits, KeySortScratch &s,
                      uint64_t **skeys, uint32_t **sslots, hipStream_t st);
-void sort_scratch_release(KeySortScratch &s);
 }  // namespace gi

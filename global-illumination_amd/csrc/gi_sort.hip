@@ -144,39 +144,16 @@ __global__ void morton_kernel(const float4 *q, int64_t n, float ox, float oy, fl
   vals[i] = (uint32_t)i;
 }
 
-// A sort scratch buffer that only grows, with the headroom rule of gi_host.cpp's DBuf: at least
-// 1/8 above the request and twice the old capacity, none when the device is short of memory.
-static hipError_t grow_scratch(void *&p, size_t &cap, size_t bytes) {
-  if (bytes <= cap && p) return hipSuccess;
-  size_t want = cap ? std::max(std::min(cap * 2, bytes + bytes / 2), bytes + bytes / 8) : bytes;
-  if (p) hipFree(p);
-  p = nullptr;
-  cap = 0;
-  if (want > bytes) {
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < want + tot / 4) want = bytes;
-  }
-  hipError_t r = hipMalloc(&p, want);
-  if (r != hipSuccess && want > bytes) {
-    (void)hipGetLastError();
-    want = bytes;
-    r = hipMalloc(&p, want);
-  }
-  if (r == hipSuccess) cap = want;
-  return r;
-}
-
 hipError_t morton_order(const float4 *q, int64_t n, const float bmin[3], const float bmax[3],
                         SortScratch &s, uint32_t **perm_out, hipStream_t st) {
   *perm_out = nullptr;
   if (n <= 0) return hipSuccess;
   hipError_t e;
-  auto grow = grow_scratch;
   size_t b4 = (size_t)n * 4;
-  if ((e = grow(s.k0, s.k0_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.k1, s.k1_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.v0, s.v0_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.v1, s.v1_cap, b4)) != hipSuccess) return e;
+  if ((e = s.k0.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.k1.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.v0.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.v1.ensure(b4)) != hipSuccess) return e;
   // 2^10 cells per axis: a 30-bit code, four 8-bit radix passes
   constexpr int bits = 10;
   const float cmax = (float)((1 << bits) - 1);
@@ -186,18 +163,18 @@ hipError_t morton_order(const float4 *q, int64_t n, const float bmin[3], const f
     sc[i] = ext > 0 ? cmax / ext : 0.0f;
   }
   morton_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-      q, n, bmin[0], bmin[1], bmin[2], sc[0], sc[1], sc[2], cmax, (uint32_t *)s.k0, (uint32_t *)s.v0);
+      q, n, bmin[0], bmin[1], bmin[2], sc[0], sc[1], sc[2], cmax, (uint32_t *)s.k0.p, (uint32_t *)s.v0.p);
   size_t tb = 0;
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0, 3 * bits,
+  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0, 3 * bits,
                                          st);
   if (e != hipSuccess) return e;
-  if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-  e = hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0, 3 * bits,
+  if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+  e = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0, 3 * bits,
                                          st);
   if (e != hipSuccess) return e;
-  *perm_out = (uint32_t *)s.v1;
+  *perm_out = (uint32_t *)s.v1.p;
   return hipSuccess;
 }
 
@@ -384,16 +361,15 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
   *nvalid = 0;
   if (n <= 0) return hipSuccess;
   hipError_t e;
-  auto grow = grow_scratch;
   size_t b4 = (size_t)n * 4;
   const bool wide = key_bits > 10;
   const size_t kb = wide ? 2 * b4 : b4;
-  if ((e = grow(s.k0, s.k0_cap, kb + 16)) != hipSuccess) return e;
-  if ((e = grow(s.k1, s.k1_cap, kb)) != hipSuccess) return e;
-  if ((e = grow(s.v0, s.v0_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.v1, s.v1_cap, b4)) != hipSuccess) return e;
+  if ((e = s.k0.ensure(kb + 16)) != hipSuccess) return e;
+  if ((e = s.k1.ensure(kb)) != hipSuccess) return e;
+  if ((e = s.v0.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.v1.ensure(b4)) != hipSuccess) return e;
   // the valid count lives past the keys (8 B, aligned)
-  auto *d_cnt = reinterpret_cast<unsigned long long *>((char *)s.k0 + ((kb + 7) & ~(size_t)7));
+  auto *d_cnt = reinterpret_cast<unsigned long long *>((char *)s.k0.p + ((kb + 7) & ~(size_t)7));
   if (wide && surf) {
     // surface keys with 16-bit in-plane cells: 8 + 32 key bits and the empty slots' bit, six
     // radix passes (the 3-D curve's 16-bit cells take seven)
@@ -407,17 +383,17 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
       emax = std::max(emax, ext);
     }
     g.siso = emax > 0 ? (float)(1u << B) / emax : 0.0f;
-    surf64_valid_kernel<B><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q, n, g, (uint64_t *)s.k0,
-                                                                        (uint32_t *)s.v0);
+    surf64_valid_kernel<B><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q, n, g, (uint64_t *)s.k0.p,
+                                                                        (uint32_t *)s.v0.p);
     size_t tb = 0;
-    e = wide_sort(nullptr, tb, (const uint64_t *)s.k0, (uint64_t *)s.k1, (const uint32_t *)s.v0,
-                  (uint32_t *)s.v1, n, 8 + 2 * B + 1, st);
+    e = wide_sort(nullptr, tb, (const uint64_t *)s.k0.p, (uint64_t *)s.k1.p, (const uint32_t *)s.v0.p,
+                  (uint32_t *)s.v1.p, n, 8 + 2 * B + 1, st);
     if (e != hipSuccess) return e;
-    if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-    e = wide_sort(s.tmp, tb, (const uint64_t *)s.k0, (uint64_t *)s.k1, (const uint32_t *)s.v0,
-                  (uint32_t *)s.v1, n, 8 + 2 * B + 1, st);
+    if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+    e = wide_sort(s.tmp.p, tb, (const uint64_t *)s.k0.p, (uint64_t *)s.k1.p, (const uint32_t *)s.v0.p,
+                  (uint32_t *)s.v1.p, n, 8 + 2 * B + 1, st);
     if (e != hipSuccess) return e;
-    first_empty_kernel<uint64_t><<<1, 64, 0, st>>>((const uint64_t *)s.k1, n, 1ull << (8 + 2 * B), d_cnt);
+    first_empty_kernel<uint64_t><<<1, 64, 0, st>>>((const uint64_t *)s.k1.p, n, 1ull << (8 + 2 * B), d_cnt);
   } else if (wide) {
     // B-bit cells, 64-bit keys: 3B + 1 key bits, (3B + 1) / 8 rounded up radix passes
     const int B = key_bits > 20 ? 20 : key_bits;
@@ -431,7 +407,7 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
 #define CURVE64_CASE(b)                                                                      \
   case b:                                                                                    \
     curve64_valid_kernel<b><<<g, 256, 0, st>>>(q, n, bmin[0], bmin[1], bmin[2], sw[0], sw[1], \
-                                               sw[2], cm, (uint64_t *)s.k0, (uint32_t *)s.v0); \
+                                               sw[2], cm, (uint64_t *)s.k0.p, (uint32_t *)s.v0.p); \
     break;
     switch (B) {
       CURVE64_CASE(11) CURVE64_CASE(12) CURVE64_CASE(13) CURVE64_CASE(14) CURVE64_CASE(15)
@@ -440,16 +416,16 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
     }
 #undef CURVE64_CASE
     size_t tb = 0;
-    e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t *)s.k0, (uint64_t *)s.k1,
-                                           (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t *)s.k0.p, (uint64_t *)s.k1.p,
+                                           (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                            3 * B + 1, st);
     if (e != hipSuccess) return e;
-    if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-    e = hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, (const uint64_t *)s.k0, (uint64_t *)s.k1,
-                                           (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+    if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+    e = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tb, (const uint64_t *)s.k0.p, (uint64_t *)s.k1.p,
+                                           (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                            3 * B + 1, st);
     if (e != hipSuccess) return e;
-    first_empty_kernel<uint64_t><<<1, 64, 0, st>>>((const uint64_t *)s.k1, n, 1ull << (3 * B), d_cnt);
+    first_empty_kernel<uint64_t><<<1, 64, 0, st>>>((const uint64_t *)s.k1.p, n, 1ull << (3 * B), d_cnt);
   } else {
   constexpr int bits = 10;
   const float cmax = (float)((1 << bits) - 1);
@@ -459,26 +435,26 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
     sc[i] = ext > 0 ? cmax / ext : 0.0f;
   }
   morton_valid_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-      q, n, bmin[0], bmin[1], bmin[2], sc[0], sc[1], sc[2], cmax, (uint32_t *)s.k0,
-      (uint32_t *)s.v0);
+      q, n, bmin[0], bmin[1], bmin[2], sc[0], sc[1], sc[2], cmax, (uint32_t *)s.k0.p,
+      (uint32_t *)s.v0.p);
   size_t tb = 0;
   // 31 key bits: the 30-bit code and the empty slots' 2^30 (four 8-bit passes, as for 30 bits)
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                          3 * bits + 1, st);
   if (e != hipSuccess) return e;
-  if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-  e = hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+  if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+  e = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                          3 * bits + 1, st);
   if (e != hipSuccess) return e;
-  first_empty_kernel<uint32_t><<<1, 64, 0, st>>>((const uint32_t *)s.k1, n, 1u << 30, d_cnt);
+  first_empty_kernel<uint32_t><<<1, 64, 0, st>>>((const uint32_t *)s.k1.p, n, 1u << 30, d_cnt);
   }
   unsigned long long nv = 0;
   if ((e = hipMemcpyAsync(&nv, d_cnt, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
   *nvalid = (int64_t)nv;
-  *perm_out = (uint32_t *)s.v1;
+  *perm_out = (uint32_t *)s.v1.p;
   return hipSuccess;
 }
 
@@ -493,38 +469,23 @@ hipError_t key_order(const uint64_t *keys, int64_t n, int key_bits, KeySortScrat
   *sslots = nullptr;
   if (n <= 0) return hipSuccess;
   hipError_t e;
-  auto grow = grow_scratch;
-  if ((e = grow(s.k1, s.k1_cap, (size_t)n * 8)) != hipSuccess) return e;
-  if ((e = grow(s.v0, s.v0_cap, (size_t)n * 4)) != hipSuccess) return e;
-  if ((e = grow(s.v1, s.v1_cap, (size_t)n * 4)) != hipSuccess) return e;
-  iota_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((uint32_t *)s.v0, n);
+  if ((e = s.k1.ensure((size_t)n * 8)) != hipSuccess) return e;
+  if ((e = s.v0.ensure((size_t)n * 4)) != hipSuccess) return e;
+  if ((e = s.v1.ensure((size_t)n * 4)) != hipSuccess) return e;
+  iota_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((uint32_t *)s.v0.p, n);
   size_t tb = 0;
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, (uint64_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, (uint64_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                          key_bits, st);
   if (e != hipSuccess) return e;
-  if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-  e = hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, keys, (uint64_t *)s.k1,
-                                         (const uint32_t *)s.v0, (uint32_t *)s.v1, (int)n, 0,
+  if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+  e = hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tb, keys, (uint64_t *)s.k1.p,
+                                         (const uint32_t *)s.v0.p, (uint32_t *)s.v1.p, (int)n, 0,
                                          key_bits, st);
   if (e != hipSuccess) return e;
-  *skeys = (uint64_t *)s.k1;
-  *sslots = (uint32_t *)s.v1;
+  *skeys = (uint64_t *)s.k1.p;
+  *sslots = (uint32_t *)s.v1.p;
   return hipSuccess;
-}
-
-void sort_scratch_release(KeySortScratch &s) {
-  void *ps[] = {s.k1, s.v0, s.v1, s.tmp};
-  for (void *p : ps)
-    if (p) hipFree(p);
-  s = KeySortScratch();
-}
-
-void sort_scratch_release(SortScratch &s) {
-  void *ps[] = {s.k0, s.k1, s.v0, s.v1, s.tmp, s.rows, s.cnt};
-  for (void *p : ps)
-    if (p) hipFree(p);
-  s = SortScratch();
 }
 
 hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmask, int64_t trows,
@@ -535,12 +496,11 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
   *nvalid = 0;
   if (nq <= 0) return hipSuccess;
   hipError_t e;
-  auto grow = grow_scratch;
   const int64_t Rp = (nprim + 63) / 64, R = Rp + trows;
-  if ((e = grow(s.rows, s.rows_cap, (size_t)(R + 1) * 8)) != hipSuccess) return e;
-  if ((e = grow(s.cnt, s.cnt_cap, (size_t)(2 * R + 2) * 4)) != hipSuccess) return e;
-  uint64_t *rows = (uint64_t *)s.rows;
-  uint32_t *cnt = (uint32_t *)s.cnt, *off = cnt + (R + 1);
+  if ((e = s.rows.ensure((size_t)(R + 1) * 8)) != hipSuccess) return e;
+  if ((e = s.cnt.ensure((size_t)(2 * R + 2) * 4)) != hipSuccess) return e;
+  uint64_t *rows = (uint64_t *)s.rows.p;
+  uint32_t *cnt = (uint32_t *)s.cnt.p, *off = cnt + (R + 1);
   if (nprim > 0) prim_rows_kernel<<<(unsigned)((nprim + 255) / 256), 256, 0, st>>>(q, nprim, rows);
   if (trows > 0 &&
       (e = hipMemcpyAsync(rows + Rp, qmask, (size_t)trows * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess)
@@ -551,8 +511,8 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
   size_t tb = 0;
   e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, off, (int)(R + 1), st);
   if (e != hipSuccess) return e;
-  if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(s.tmp, tb, cnt, off, (int)(R + 1), st);
+  if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+  e = hipcub::DeviceScan::ExclusiveSum(s.tmp.p, tb, cnt, off, (int)(R + 1), st);
   if (e != hipSuccess) return e;
   uint32_t ndet = 0;
   if ((e = hipMemcpyAsync(&ndet, off + R, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
@@ -561,10 +521,10 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
   const int64_t n = (int64_t)ndet + napp;
   if (n == 0) return hipSuccess;
   size_t b4 = (size_t)n * 4;
-  if ((e = grow(s.k0, s.k0_cap, b4 + 16)) != hipSuccess) return e;
-  if ((e = grow(s.k1, s.k1_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.v0, s.v0_cap, b4)) != hipSuccess) return e;
-  if ((e = grow(s.v1, s.v1_cap, b4)) != hipSuccess) return e;
+  if ((e = s.k0.ensure(b4 + 16)) != hipSuccess) return e;
+  if ((e = s.k1.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.v0.ensure(b4)) != hipSuccess) return e;
+  if ((e = s.v1.ensure(b4)) != hipSuccess) return e;
   constexpr int bits = 10;
   KeyGeom g;
   g.cmax = (float)((1 << bits) - 1);
@@ -580,22 +540,22 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
   g.surf = surf ? 1 : 0;
   if (R > 0)
     row_keys_kernel<<<(unsigned)((R + 255) / 256), 256, 0, st>>>(rows, off, Rp, R, nprim, q, g,
-                                                             (uint32_t *)s.k0, (uint32_t *)s.v0);
+                                                             (uint32_t *)s.k0.p, (uint32_t *)s.v0.p);
   if (napp > 0)
     append_keys_kernel<<<(unsigned)((napp + 255) / 256), 256, 0, st>>>(
-        q, qbase, napp, (int64_t)ndet, g, (uint32_t *)s.k0, (uint32_t *)s.v0);
+        q, qbase, napp, (int64_t)ndet, g, (uint32_t *)s.k0.p, (uint32_t *)s.v0.p);
   // every compacted slot holds a query (the masks say so), so every key is below 2^30: 30 key
   // bits, and no count of the valid ones
   tb = 0;
-  e = row_sort(nullptr, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1, (const uint32_t *)s.v0,
-               (uint32_t *)s.v1, n, st);
+  e = row_sort(nullptr, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p, (const uint32_t *)s.v0.p,
+               (uint32_t *)s.v1.p, n, st);
   if (e != hipSuccess) return e;
-  if ((e = grow(s.tmp, s.tmp_cap, tb + 256)) != hipSuccess) return e;
-  e = row_sort(s.tmp, tb, (const uint32_t *)s.k0, (uint32_t *)s.k1, (const uint32_t *)s.v0,
-               (uint32_t *)s.v1, n, st);
+  if ((e = s.tmp.ensure(tb + 256)) != hipSuccess) return e;
+  e = row_sort(s.tmp.p, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p, (const uint32_t *)s.v0.p,
+               (uint32_t *)s.v1.p, n, st);
   if (e != hipSuccess) return e;
   *nvalid = n;
-  *perm_out = (uint32_t *)s.v1;
+  *perm_out = (uint32_t *)s.v1.p;
   return hipSuccess;
 }
 

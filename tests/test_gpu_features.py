@@ -323,7 +323,7 @@ def test_device_set_matches_one_device(devices, name, extra):
 ])
 def test_single_pass_photon_maps_equal_two_pass(name, extra, rate0, monkeypatch):
     """Single-pass photon tracing (one atomic per wave per bounce, then a sort on (emission
-    index, store ordinal); gi_host.cpp trace_batch_dev) builds the maps the count pass + scan +
+    index, store ordinal); gi_photons.cpp trace_batch_dev) builds the maps the count pass + scan +
     re-trace (GI_PHOTON_2PASS=1, r03) built: byte for byte, in the same emission order, with the
     same emitted counts. Covers several lights and emission rounds (stilllife), a short -pd
     (few ordinal bits), and launches that overflow their first slot estimate and are re-run

@@ -379,3 +379,65 @@ def test_knn_instances_without_general_form_are_exact(monkeypatch):
     np.testing.assert_array_equal(out[0][0], out[1][0])
     for k in ("knn_queries", "knn_photons", "caustic_samples", "indirect_samples"):
         assert out[0][1][k] == out[1][1][k], k
+
+
+SMALL = [scene("cornell.scn"), "/tmp/x.png", "-resolution", "24", "16", "-aa", "1", "-global", "4000",
+         "-caustic", "4000", "-it", "8", "-tt", "4", "-st", "4", "-seed", "3"]
+
+
+def test_released_scratch_changes_no_bits_and_keeps_state():
+    """gi_release_scratch frees every scratch buffer and nothing else: a frame, two accumulator
+    passes, the release, a third pass, the accumulator read back and the frame again give, bit
+    for bit, what the same sequence gives on a context that never released. So the photon maps,
+    the counters, the accumulator and its counts survive the release, and everything else is
+    allocated again by the call that needs it."""
+    p, sc, _o, w, h, aa, real = gi_amd.ParseArgs(SMALL)
+    out = []
+    for release in (True, False):
+        r = gi_amd.Renderer(0, p)
+        try:
+            r.ReadScene(sc, real)
+            r.MapPhotons()
+            first, _ = r.RenderImage(aa, w, h)
+            r.accum_reset(w, h)
+            for i in range(3):
+                if i == 2 and release:
+                    r.release_scratch()
+                p.seed = 3 + i
+                r.set_params(p)
+                r.accum_add_image(aa)
+            p.seed = 3
+            r.set_params(p)
+            mean, var, n, noise = r.accum_get()
+            counts, total = r.accum_get_counts()
+            again, _ = r.RenderImage(aa, w, h)
+            out.append((first, again, mean, var, counts, n, total, noise))
+        finally:
+            r.close()
+    a, b = out
+    assert a[5] == b[5] == 3 * 4 ** aa and a[6] == b[6] == w * h * 3 * 4 ** aa
+    assert a[7] == b[7]
+    assert np.isfinite(a[2]).all() and a[2].max() > 0
+    for x, y in zip(a[:5], b[:5]):
+        np.testing.assert_array_equal(x, y)
+    np.testing.assert_array_equal(a[0], a[1])
+
+
+def test_contexts_come_and_go():
+    """Create, load, map, render and close a context four times in one process, then once more
+    as a two-entry device set on one GPU: the five frames are the same (the buffers' destructors
+    and the peers' destroy order leave nothing behind that the next context could meet)."""
+    import hashlib
+    p, sc, _o, w, h, aa, real = gi_amd.ParseArgs(SMALL)
+    hashes = []
+    for devs in (None, None, None, None, [0, 0]):
+        r = gi_amd.Renderer(0, p, devices=devs)
+        try:
+            r.ReadScene(sc, real)
+            r.MapPhotons()
+            rgb, _ = r.RenderImage(aa, w, h)
+            hashes.append(hashlib.sha256(rgb.tobytes()).hexdigest())
+        finally:
+            r.close()
+    assert rgb.max() > 0
+    assert len(set(hashes)) == 1, hashes

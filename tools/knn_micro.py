@@ -5,7 +5,7 @@ Photon maps: cornell.scn, 1M global + 1M caustic photons (bench.py's C2 maps).
 Queries: surface points hit by rays from random points inside the box in random directions
 (the distribution of Monte Carlo bounce vertices), Morton-ordered inside gi_knn_bench.
 
-Tuning knobs are environment variables read when a context is created (gi_host.cpp):
+Tuning knobs are environment variables read when a context is created (gi_context.cpp gi_create):
   --env GI_LEAF_SIZE=32,64 --env GI_LANE_CHUNK=4,8   sweeps their cartesian product.
 Prints one line per (knob setting, map, kernel, mode): ms per launch, ns per query, photons
 found and photons visited per query.
