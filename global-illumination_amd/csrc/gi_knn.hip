@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include "gi_device.h"
 #include "gi_kernels.h"
+#include "gi_estimate.h"
 
 namespace gi {
 
@@ -33,6 +34,7 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ C3 wave_sum(C3 v) { return rgb(wave_sum(v.r), wave_sum(v.g), wave_sum(v.b)); }
 
 // Wave-level radix select over the candidate buffer buf[0, count): find the K-th smallest
 // key T, keep exactly the keys <= T (compacted to buf[0, K)) and set thr = T (a later
@@ -169,7 +171,7 @@ __device__ __forceinline__ void wave_estimate(const KnnArgs &a, int64_t qi, floa
   const int lane = threadIdx.x;
   const int K = a.K;
   double maxd2 = kEps;
-  double o0 = 0, o1 = 0, o2 = 0;
+  C3 o = rgb(0.0, 0.0, 0.0);
   if (num > 0) {
     if (num < K) {
       maxd2 = a.rmax * a.rmax;
@@ -180,44 +182,19 @@ __device__ __forceinline__ void wave_estimate(const KnnArgs &a, int64_t qi, floa
         lm = d > lm ? d : lm;
       }
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        double t = __shfl_xor(lm, o, 64);
+      for (int x = 32; x > 0; x >>= 1) {
+        double t = __shfl_xor(lm, x, 64);
         lm = t > lm ? t : lm;
       }
       if (lm > maxd2) maxd2 = lm;
     }
     if (a.mode == KNN_MODE_IRRADIANCE) {
-      for (int s = lane; s < num; s += 64) {
-        uint32_t e = a.map.rgbe[fetch_id(s)];
-        uint32_t ee = e >> 24;
-        if (ee) {
-          double inv = ldexp(1.0, (int)ee - 128 - 8);
-          o0 += (double)(e & 255u) * inv;
-          o1 += (double)((e >> 8) & 255u) * inv;
-          o2 += (double)((e >> 16) & 255u) * inv;
-        }
-      }
-      o0 = wave_sum(o0); o1 = wave_sum(o1); o2 = wave_sum(o2);
-      double den = kPi * maxd2;
-      o0 /= den; o1 /= den; o2 /= den;
+      for (int s = lane; s < num; s += 64) irradiance_add(a.map.rgbe[fetch_id(s)], o);
+      o = irradiance_finish(wave_sum(o), maxd2);
     } else {
-      const QShade &sh = a.qshade[qi];
-      uint32_t meta = __float_as_uint(qp.w);
-      uint32_t sign = meta & 3u;
-      const DMaterial &m = a.mats[qmeta_mat(meta)];
-      double N0 = sh.n[0], N1 = sh.n[1], N2 = sh.n[2];
-      double E0 = sh.ex[0], E1 = sh.ex[1], E2 = sh.ex[2];
-      bool spec = (m.flags & MF_SPECULAR) || (m.n < 0);
-      // without the specular term, ap * kd + 0 * ks == ap * kd up to the sign of a zero (for
-      // finite ks), and the sums start at +0, so dropping the 0 * ks products changes no result
-      const bool diff_only = !spec && isfinite(m.ks[0]) && isfinite(m.ks[1]) && isfinite(m.ks[2]);
-      double c1 = 1.0, c2 = 1.0, tw = 0;
-      if (a.filter == 1) c1 = 1.0 / (a.fk * sqrt(maxd2));
-      else if (a.filter == 2) {
-        c1 = pow_call(2.7182818284590452354, -a.fb);
-        c2 = 1.0 / (2.0 * maxd2);
-      }
-      if (a.filter == 0 && diff_only) {
+      const EstQuery Q(a, qi, qp.w, maxd2);
+      double tw = 0;
+      if (a.filter == 0 && Q.diff_only) {
         // common case (disk filter, no specular term): the lane's photons s, s + 64, ... in
         // groups of four, their list, direction-code, rgbe and LUT loads in flight together;
         // each lane still sums its photons in increasing s
@@ -228,102 +205,39 @@ __device__ __forceinline__ void wave_estimate(const KnnArgs &a, int64_t qi, floa
           for (int u = 0; u < 4; u++) ids[u] = fetch_id(s0 + 64 * u < num ? s0 + 64 * u : s0);
 #pragma unroll
           for (int u = 0; u < 4; u++) {
-            dcs[u] = __float_as_uint(a.map.pos4[4 * (int64_t)ids[u] + 3]) & 0xffffu;
+            dcs[u] = photon_dcode(a, ids[u]);
             ee[u] = a.map.rgbe[ids[u]];
           }
 #pragma unroll
-          for (int u = 0; u < 4; u++) {
-            lx[u] = a.lut[3 * dcs[u]];
-            ly[u] = a.lut[3 * dcs[u] + 1];
-            lz[u] = a.lut[3 * dcs[u] + 2];
-          }
+          for (int u = 0; u < 4; u++) lut_dir(a, dcs[u], lx[u], ly[u], lz[u]);
 #pragma unroll
           for (int u = 0; u < 4; u++) {
             if (s0 + 64 * u >= num) break;
-            double perp = N0 * lx[u] + N1 * ly[u] + N2 * lz[u];
-            if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-            uint32_t e = ee[u];
-            uint32_t x = e >> 24;
-            double inv = x ? ldexp(1.0, (int)x - 128 - 8) : 0.0;
-            double p0 = x ? (double)(e & 255u) * inv : 0.0;
-            double p1 = x ? (double)((e >> 8) & 255u) * inv : 0.0;
-            double p2 = x ? (double)((e >> 16) & 255u) * inv : 0.0;
-            double ap = fabs(perp);
-            p0 *= ap * m.kd[0];
-            p1 *= ap * m.kd[1];
-            p2 *= ap * m.kd[2];
-            o0 += p0; o1 += p1; o2 += p2;
+            double perp = Q.perp(lx[u], ly[u], lz[u]);
+            if (Q.wrong_side(perp)) continue;
+            o = o + Q.disk_term_kd(perp, ee[u]);
           }
         }
       } else if constexpr (!GEN) {
-        o0 = o1 = o2 = __builtin_nan("");  // see chunk_estimate: the host's check failed
-        if (a.stats) atomicAdd(a.stats + ST_GEN_MISS, 1ull);
+        o = est_gen_miss(a);
       } else
       for (int s = lane; s < num; s += 64) {
         uint32_t id = fetch_id(s);
         double d2 = (double)fetch_d2(s);
-        uint32_t dcode = __float_as_uint(a.map.pos4[4 * (int64_t)id + 3]) & 0xffffu;
-        double ix = a.lut[3 * dcode], iy = a.lut[3 * dcode + 1], iz = a.lut[3 * dcode + 2];
-        double perp = N0 * ix + N1 * iy + N2 * iz;
-        if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-        uint32_t e = a.map.rgbe[id];
-        uint32_t ee = e >> 24;
-        double inv = ee ? ldexp(1.0, (int)ee - 128 - 8) : 0.0;
-        double p0 = ee ? (double)(e & 255u) * inv : 0.0;
-        double p1 = ee ? (double)((e >> 8) & 255u) * inv : 0.0;
-        double p2 = ee ? (double)((e >> 16) & 255u) * inv : 0.0;
-        double ca = E0 * -ix + E1 * -iy + E2 * -iz;
-        if (ca < 0) ca = 0;
-        double ap = fabs(perp);
-        if (diff_only) {
-          p0 *= ap * m.kd[0];
-          p1 *= ap * m.kd[1];
-          p2 *= ap * m.kd[2];
-        } else {
-          double pw = spec ? pow_call(ca, m.n) : 0.0;
-          p0 *= ap * m.kd[0] + pw * m.ks[0];
-          p1 *= ap * m.kd[1] + pw * m.ks[1];
-          p2 *= ap * m.kd[2] + pw * m.ks[2];
-        }
-        if (a.filter == 1) {
-          double f = (1.0 - c1 * sqrt(d2));
-          p0 *= f; p1 *= f; p2 *= f;
-        } else if (a.filter == 2) {
-          double w = (1.0 - (1.0 - pow_call(c1, c2 * d2)) / (1.0 - c1));
-          p0 *= w; p1 *= w; p2 *= w;
-          tw += w;
-        }
-        o0 += p0; o1 += p1; o2 += p2;
+        double ix, iy, iz;
+        lut_dir(a, photon_dcode(a, id), ix, iy, iz);
+        double perp = Q.perp(ix, iy, iz);
+        if (Q.wrong_side(perp)) continue;
+        C3 p;
+        Q.general_term(a, Q.E, ix, iy, iz, perp, a.map.rgbe[id], d2, p, tw);
+        o = o + p;
       }
-      o0 = wave_sum(o0); o1 = wave_sum(o1); o2 = wave_sum(o2);
+      o = wave_sum(o);
       if (a.filter == 2) tw = wave_sum(tw);
-      bool ok = true;
-      if (a.filter == 0 && maxd2 > 0) {
-        double den = kPi * maxd2;
-        o0 /= den; o1 /= den; o2 /= den;
-      } else if (a.filter == 1 && maxd2 > 0) {
-        double den = (1.0 - 2.0 / 3.0 / a.fk) * kPi * maxd2;
-        o0 /= den; o1 /= den; o2 /= den;
-      } else if (a.filter == 2 && tw > 0 && maxd2 > 0) {
-        double sc = a.fa * (num / tw) / (kPi * maxd2);
-        o0 *= sc; o1 *= sc; o2 *= sc;
-      } else {
-        ok = false;
-      }
-      if (ok) {
-        o0 *= sh.w[0]; o1 *= sh.w[1]; o2 *= sh.w[2];
-      } else {
-        o0 = o1 = o2 = 0;
-      }
+      est_finish(a, a.filter, Q.sh, num, maxd2, tw, o);
     }
   }
-  if (lane == 0) {
-    a.out[3 * qi] = o0;
-    a.out[3 * qi + 1] = o1;
-    a.out[3 * qi + 2] = o2;
-    if (a.out_n) a.out_n[qi] = num;
-    if (a.out_maxd2) a.out_maxd2[qi] = (num > 0) ? (float)maxd2 : 0.0f;
-  }
+  if (lane == 0) est_store(a, qi, num, maxd2, o);
 }
 
 #ifndef WAVE_WPE
@@ -456,8 +370,7 @@ void knn_wave_kernel(KnnArgs a) {
                 if (ii < s1) {
                   float4 p = pos[ii];
                   float dkp = a.map.dk[ii];
-                  float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                  float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+                  float d2 = photon_d2(qx, qy, qz, p.x, p.y, p.z);
                   if (dkp < INFINITY) best = fmin(best, sqrt((double)d2 * (1.0 + 1e-5)) + (double)dkp);
                 }
               }
@@ -487,8 +400,7 @@ void knn_wave_kernel(KnnArgs a) {
               uint64_t key = ~0ull;
               if (ii < s1) {
                 float4 p = pf[u];
-                float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+                float d2 = photon_d2(qx, qy, qz, p.x, p.y, p.z);
                 key = ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)(uint32_t)ii;
               }
               bool pass = key < thr;
@@ -545,8 +457,7 @@ void knn_wave_kernel(KnnArgs a) {
           if (ii < s1) {
             float4 p = pos[ii];
             float dkp = a.map.dk[ii];
-            float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-            float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+            float d2 = photon_d2(qx, qy, qz, p.x, p.y, p.z);
             // fp32 metric -> true distance: 1e-5 relative margin
             if (dkp < INFINITY) best = fmin(best, sqrt((double)d2 * (1.0 + 1e-5)) + (double)dkp);
           }
@@ -618,8 +529,7 @@ void knn_wave_kernel(KnnArgs a) {
               uint64_t key = ~0ull;
               if (ii < s1) {
                 float4 p = pf[u];
-                float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-                float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+                float d2 = photon_d2(qx, qy, qz, p.x, p.y, p.z);
                 key = ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)(uint32_t)ii;
               }
               bool pass = key < thr;
@@ -837,8 +747,7 @@ __global__ __launch_bounds__(64) void knn_lane_kernel(KnnArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < CH; u++) {
-          float dx = qp.x - p[u].x, dy = qp.y - p[u].y, dz = qp.z - p[u].z;
-          float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+          float d2 = photon_d2(qp.x, qp.y, qp.z, p[u].x, p[u].y, p[u].z);
           uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)(uint32_t)(ii + u);
           if (ii + u < s1 && key < lim) heapn_accept<ARY>(h, size, K, key, lim);
           if (seed) {
@@ -871,45 +780,19 @@ __global__ __launch_bounds__(64) void knn_lane_kernel(KnnArgs a) {
       }
       a.out_n[qi] = num;
     } else {
-      double o0 = 0, o1 = 0, o2 = 0;
+      C3 o = rgb(0.0, 0.0, 0.0);
       double maxd2 = kEps;
       if (num > 0) {
         // max-heap root = K-th distance (photon_utils.cpp:108-111); r_max^2 if fewer (Q4)
         maxd2 = (num < K) ? a.rmax * a.rmax : (double)__uint_as_float((uint32_t)(h[0] >> 32));
         if (num == K && maxd2 < kEps) maxd2 = kEps;
         if (a.mode == KNN_MODE_IRRADIANCE) {
-          // EstimateIrradiance, photon_utils.cpp:209-246
-          for (int s = 0; s < num; s++) {
-            uint32_t e = a.map.rgbe[(uint32_t)h[s * 64]];
-            uint32_t ex = e >> 24;
-            if (ex) {
-              double inv = ldexp(1.0, (int)ex - 128 - 8);
-              o0 += (double)(e & 255u) * inv;
-              o1 += (double)((e >> 8) & 255u) * inv;
-              o2 += (double)((e >> 16) & 255u) * inv;
-            }
-          }
-          double den = kPi * maxd2;
-          o0 /= den; o1 /= den; o2 /= den;
+          for (int s = 0; s < num; s++) irradiance_add(a.map.rgbe[(uint32_t)h[s * 64]], o);
+          o = irradiance_finish(o, maxd2);
         } else {
-          // EstimateRadiance, photon_utils.cpp:113-158
-          const QShade &sh = a.qshade[qi];
-          uint32_t meta = __float_as_uint(qp.w);
-          uint32_t sign = meta & 3u;
-          const DMaterial &m = a.mats[qmeta_mat(meta)];
-          double N0 = sh.n[0], N1 = sh.n[1], N2 = sh.n[2];
-          double E0 = sh.ex[0], E1 = sh.ex[1], E2 = sh.ex[2];
-          bool spec = (m.flags & MF_SPECULAR) || (m.n < 0);
-          // without the specular term, ap * kd + 0 * ks == ap * kd up to the sign of a zero (for
-          // finite ks), and the sums start at +0, so dropping the 0 * ks products changes no result
-          const bool diff_only = !spec && isfinite(m.ks[0]) && isfinite(m.ks[1]) && isfinite(m.ks[2]);
-          double c1 = 1.0, c2 = 1.0, tw = 0;
-          if (a.filter == 1) c1 = 1.0 / (a.fk * sqrt(maxd2));
-          else if (a.filter == 2) {
-            c1 = pow_call(2.7182818284590452354, -a.fb);
-            c2 = 1.0 / (2.0 * maxd2);
-          }
-          if (a.filter == 0 && diff_only) {
+          const EstQuery Q(a, qi, qp.w, maxd2);
+          double tw = 0;
+          if (a.filter == 0 && Q.diff_only) {
             // common case (disk filter, no specular term): photons in groups of four, the heap
             // slot, direction-code, rgbe and LUT loads of a group in flight together; the sum
             // runs in slot order as in the general loop below
@@ -921,31 +804,17 @@ __global__ __launch_bounds__(64) void knn_lane_kernel(KnnArgs a) {
               uint32_t dcs[4];
 #pragma unroll
               for (int u = 0; u < 4; u++) {
-                dcs[u] = __float_as_uint(a.map.pos4[4 * (int64_t)ids[u] + 3]) & 0xffffu;
+                dcs[u] = photon_dcode(a, ids[u]);
                 ee[u] = a.map.rgbe[ids[u]];
               }
 #pragma unroll
-              for (int u = 0; u < 4; u++) {
-                lx[u] = a.lut[3 * dcs[u]];
-                ly[u] = a.lut[3 * dcs[u] + 1];
-                lz[u] = a.lut[3 * dcs[u] + 2];
-              }
+              for (int u = 0; u < 4; u++) lut_dir(a, dcs[u], lx[u], ly[u], lz[u]);
 #pragma unroll
               for (int u = 0; u < 4; u++) {
                 if (s0 + u >= num) break;
-                double perp = N0 * lx[u] + N1 * ly[u] + N2 * lz[u];
-                if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-                uint32_t e = ee[u];
-                uint32_t x = e >> 24;
-                double inv = x ? ldexp(1.0, (int)x - 128 - 8) : 0.0;
-                double p0 = x ? (double)(e & 255u) * inv : 0.0;
-                double p1 = x ? (double)((e >> 8) & 255u) * inv : 0.0;
-                double p2 = x ? (double)((e >> 16) & 255u) * inv : 0.0;
-                double ap = fabs(perp);
-                p0 *= ap * m.kd[0];
-                p1 *= ap * m.kd[1];
-                p2 *= ap * m.kd[2];
-                o0 += p0; o1 += p1; o2 += p2;
+                double perp = Q.perp(lx[u], ly[u], lz[u]);
+                if (Q.wrong_side(perp)) continue;
+                o = o + Q.disk_term_kd(perp, ee[u]);
               }
             }
           } else
@@ -953,64 +822,18 @@ __global__ __launch_bounds__(64) void knn_lane_kernel(KnnArgs a) {
             uint64_t key = h[s * 64];
             uint32_t id = (uint32_t)key;
             double d2 = (double)__uint_as_float((uint32_t)(key >> 32));
-            uint32_t dcode = __float_as_uint(a.map.pos4[4 * (int64_t)id + 3]) & 0xffffu;
-            double ix = a.lut[3 * dcode], iy = a.lut[3 * dcode + 1], iz = a.lut[3 * dcode + 2];
-            double perp = N0 * ix + N1 * iy + N2 * iz;
-            if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-            uint32_t e = a.map.rgbe[id];
-            uint32_t ee = e >> 24;
-            double inv = ee ? ldexp(1.0, (int)ee - 128 - 8) : 0.0;
-            double p0 = ee ? (double)(e & 255u) * inv : 0.0;
-            double p1 = ee ? (double)((e >> 8) & 255u) * inv : 0.0;
-            double p2 = ee ? (double)((e >> 16) & 255u) * inv : 0.0;
-            double ca = E0 * -ix + E1 * -iy + E2 * -iz;
-            if (ca < 0) ca = 0;
-            double ap = fabs(perp);
-            if (diff_only) {
-              p0 *= ap * m.kd[0];
-              p1 *= ap * m.kd[1];
-              p2 *= ap * m.kd[2];
-            } else {
-              double pw = spec ? pow_call(ca, m.n) : 0.0;
-              p0 *= ap * m.kd[0] + pw * m.ks[0];
-              p1 *= ap * m.kd[1] + pw * m.ks[1];
-              p2 *= ap * m.kd[2] + pw * m.ks[2];
-            }
-            if (a.filter == 1) {
-              double f = (1.0 - c1 * sqrt(d2));
-              p0 *= f; p1 *= f; p2 *= f;
-            } else if (a.filter == 2) {
-              double w = (1.0 - (1.0 - pow_call(c1, c2 * d2)) / (1.0 - c1));
-              p0 *= w; p1 *= w; p2 *= w;
-              tw += w;
-            }
-            o0 += p0; o1 += p1; o2 += p2;
+            double ix, iy, iz;
+            lut_dir(a, photon_dcode(a, id), ix, iy, iz);
+            double perp = Q.perp(ix, iy, iz);
+            if (Q.wrong_side(perp)) continue;
+            C3 p;
+            Q.general_term(a, Q.E, ix, iy, iz, perp, a.map.rgbe[id], d2, p, tw);
+            o = o + p;
           }
-          bool ok = true;
-          if (a.filter == 0 && maxd2 > 0) {
-            double den = kPi * maxd2;
-            o0 /= den; o1 /= den; o2 /= den;
-          } else if (a.filter == 1 && maxd2 > 0) {
-            double den = (1.0 - 2.0 / 3.0 / a.fk) * kPi * maxd2;
-            o0 /= den; o1 /= den; o2 /= den;
-          } else if (a.filter == 2 && tw > 0 && maxd2 > 0) {
-            double sc = a.fa * (num / tw) / (kPi * maxd2);
-            o0 *= sc; o1 *= sc; o2 *= sc;
-          } else {
-            ok = false;
-          }
-          if (ok) {
-            o0 *= sh.w[0]; o1 *= sh.w[1]; o2 *= sh.w[2];
-          } else {
-            o0 = o1 = o2 = 0;
-          }
+          est_finish(a, a.filter, Q.sh, num, maxd2, tw, o);
         }
       }
-      a.out[3 * qi] = o0;
-      a.out[3 * qi + 1] = o1;
-      a.out[3 * qi + 2] = o2;
-      if (a.out_n) a.out_n[qi] = num;
-      if (a.out_maxd2) a.out_maxd2[qi] = (num > 0) ? (float)maxd2 : 0.0f;
+      est_store(a, qi, num, maxd2, o);
     }
   }
   if (a.stats) {

@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "gi_device.h"
 #include "gi_kernels.h"
+#include "gi_estimate.h"
 
 namespace gi {
 
@@ -66,10 +67,8 @@ __device__ __forceinline__ float wave_sort(float v, int lane) {
   return v;
 }
 
-// photon metric: the reference's squared distance in fp32, one fixed operation order
 __device__ __forceinline__ float metric(float qx, float qy, float qz, const float4 &p) {
-  float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-  return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+  return photon_d2(qx, qy, qz, p.x, p.y, p.z);
 }
 
 // The chunk's LDS candidates, structure of arrays: x[CAPC], y[CAPC], z[CAPC], w[CAPC] (w = the
@@ -605,47 +604,24 @@ __device__ __forceinline__ void chunk_estimate(const KnnArgs &a, int64_t qi, flo
                                                SlotAt slot_at) {
   const int K = a.K;
   double maxd2 = kEps;
-  double o0 = 0, o1 = 0, o2 = 0, tw = 0;
+  C3 o = rgb(0.0, 0.0, 0.0);
   if (num > 0) {
     maxd2 = (num < K) ? a.rmax * a.rmax : (double)km;
     if (num == K && maxd2 < kEps) maxd2 = kEps;
     if (a.mode == KNN_MODE_IRRADIANCE) {
-      for (int s = 0; s < num; s++) {
-        uint32_t e = crgbe[slot_at(s)];
-        uint32_t ex = e >> 24;
-        if (ex) {
-          double inv = ldexp(1.0, (int)ex - 128 - 8);
-          o0 += (double)(e & 255u) * inv;
-          o1 += (double)((e >> 8) & 255u) * inv;
-          o2 += (double)((e >> 16) & 255u) * inv;
-        }
-      }
-      double den = kPi * maxd2;
-      o0 /= den; o1 /= den; o2 /= den;
+      for (int s = 0; s < num; s++) irradiance_add(crgbe[slot_at(s)], o);
+      o = irradiance_finish(o, maxd2);
     } else {
-      const QShade &sh = a.qshade[qi];
-      uint32_t meta = __float_as_uint(qp.w);
-      uint32_t sign = meta & 3u;
-      const DMaterial &mt = a.mats[qmeta_mat(meta)];
-      double N0 = sh.n[0], N1 = sh.n[1], N2 = sh.n[2];
-      bool spec = (mt.flags & MF_SPECULAR) || (mt.n < 0);
-      // without the specular term, ap * kd + 0 * ks == ap * kd up to the sign of a zero (for
-      // finite ks), and the sums start at +0, so dropping the 0 * ks products changes no result
-      const bool diff_only = !spec && isfinite(mt.ks[0]) && isfinite(mt.ks[1]) && isfinite(mt.ks[2]);
-      double c1 = 1.0, c2 = 1.0;
-      if (a.filter == 1) c1 = 1.0 / (a.fk * sqrt(maxd2));
-      else if (a.filter == 2) {
-        c1 = pow_call(2.7182818284590452354, -a.fb);
-        c2 = 1.0 / (2.0 * maxd2);
-      }
-      // photons in groups of EB: the LDS slot reads and direction-LUT loads of a group are
-      // issued before its arithmetic (one memory round trip per group, not per photon); the
-      // sums still run in photon order
-      constexpr int EB = CHUNK_EST_EB;
-      if (a.filter == 0 && diff_only) {
+      const EstQuery Q(a, qi, qp.w, maxd2);
+      double tw = 0;
+      if (a.filter == 0 && Q.diff_only) {
         // the common case (disk filter, no specular term): neither d2 nor the exact bounce is
-        // needed, so only the direction code (w bits) and the rgbe word are read
-        const double kd0 = mt.kd[0], kd1 = mt.kd[1], kd2 = mt.kd[2];
+        // needed, so only the direction code (w bits) and the rgbe word are read. Photons in
+        // groups of EB: the LDS slot reads and direction-LUT loads of a group are issued before
+        // its arithmetic (one memory round trip per group, not per photon); the sums still run
+        // in photon order
+        constexpr int EB = CHUNK_EST_EB;
+        const C3 kd = ldc(Q.m.kd);
         for (int s0 = 0; s0 < num; s0 += EB) {
           uint32_t eg[EB];
           double lg[EB][3];
@@ -653,121 +629,43 @@ __device__ __forceinline__ void chunk_estimate(const KnnArgs &a, int64_t qi, flo
           for (int u = 0; u < EB; u++) {
             uint32_t slot = slot_at(s0 + u < num ? s0 + u : s0);
             eg[u] = crgbe[slot];
-            uint32_t dc = __float_as_uint(cpos.wbits(slot)) & 0xffffu;
-            lg[u][0] = a.lut[3 * dc];
-            lg[u][1] = a.lut[3 * dc + 1];
-            lg[u][2] = a.lut[3 * dc + 2];
+            lut_dir(a, __float_as_uint(cpos.wbits(slot)) & 0xffffu, lg[u][0], lg[u][1], lg[u][2]);
           }
-          // per photon (byte * 2^(e - 136)) * |perp|; kd multiplies the sums once per query
-          // (re-associated like the sum order: relative 1e-16 per term). The same terms as
-          // chunk_estimate_shared's, bit for bit.
+          // kd multiplies the sums once per query (re-associated like the sum order: relative
+          // 1e-16 per term). The same terms as chunk_estimate_shared's, bit for bit.
 #pragma unroll
           for (int u = 0; u < EB; u++) {
             if (s0 + u >= num) break;
-            double ix = lg[u][0], iy = lg[u][1], iz = lg[u][2];
-            double perp = N0 * ix + N1 * iy + N2 * iz;
-            if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-            uint32_t e = eg[u];
-            uint32_t ee = e >> 24;
-            double inv = ee ? ldexp(1.0, (int)ee - 128 - 8) : 0.0;
-            double p0 = ee ? (double)(e & 255u) * inv : 0.0;
-            double p1 = ee ? (double)((e >> 8) & 255u) * inv : 0.0;
-            double p2 = ee ? (double)((e >> 16) & 255u) * inv : 0.0;
-            double ap = fabs(perp);
-            p0 *= ap; p1 *= ap; p2 *= ap;
-            o0 += p0; o1 += p1; o2 += p2;
+            double perp = Q.perp(lg[u][0], lg[u][1], lg[u][2]);
+            if (Q.wrong_side(perp)) continue;
+            o = o + disk_term(perp, eg[u]);
           }
         }
-        o0 *= kd0; o1 *= kd1; o2 *= kd2;
+        o = o * kd;
       } else if constexpr (!GEN) {
-        // an instance without the general form (KnnArgs::general == 0) met a query that needs
-        // it: the host's check failed. Count it (the host re-runs the render with the general
-        // instances, gi_host.cpp render_common) and make the result unmistakable meanwhile
-        o0 = o1 = o2 = __builtin_nan("");
-        if (a.stats) atomicAdd(a.stats + ST_GEN_MISS, 1ull);
+        o = est_gen_miss(a);
       } else {
-      // one photon per step here: this path calls pow (specular term, Gauss filter), and a
-      // group of photons held across those calls would cost the whole kernel registers
-      constexpr int EB1 = 1;
-      const double E0 = sh.ex[0], E1 = sh.ex[1], E2 = sh.ex[2];
-      for (int s0 = 0; s0 < num; s0 += EB1) {
-      float4 pg[EB1];
-      uint32_t eg[EB1];
-      double lg[EB1][3];
-#pragma unroll
-      for (int u = 0; u < EB1; u++) {
-        uint32_t slot = slot_at(s0 + u < num ? s0 + u : s0);
-        pg[u] = cpos.get(slot);
-        eg[u] = crgbe[slot];
-        uint32_t dc = __float_as_uint(pg[u].w) & 0xffffu;
-        lg[u][0] = a.lut[3 * dc];
-        lg[u][1] = a.lut[3 * dc + 1];
-        lg[u][2] = a.lut[3 * dc + 2];
-      }
-#pragma unroll
-      for (int u = 0; u < EB1; u++) {
-        if (s0 + u >= num) break;
-        float4 p = pg[u];
-        double d2 = (double)metric(qp.x, qp.y, qp.z, p);
-        double ix = lg[u][0], iy = lg[u][1], iz = lg[u][2];
-        double perp = N0 * ix + N1 * iy + N2 * iz;
-        if ((sign == 2u && perp < 0) || (sign == 1u && perp > 0)) continue;
-        uint32_t e = eg[u];
-        uint32_t ee = e >> 24;
-        double inv = ee ? ldexp(1.0, (int)ee - 128 - 8) : 0.0;
-        double p0 = ee ? (double)(e & 255u) * inv : 0.0;
-        double p1 = ee ? (double)((e >> 8) & 255u) * inv : 0.0;
-        double p2 = ee ? (double)((e >> 16) & 255u) * inv : 0.0;
-        double ca = E0 * -ix + E1 * -iy + E2 * -iz;
-        if (ca < 0) ca = 0;
-        double ap = fabs(perp);
-        if (diff_only) {
-          p0 *= ap * mt.kd[0];
-          p1 *= ap * mt.kd[1];
-          p2 *= ap * mt.kd[2];
-        } else {
-          double pw = spec ? pow_call(ca, mt.n) : 0.0;
-          p0 *= ap * mt.kd[0] + pw * mt.ks[0];
-          p1 *= ap * mt.kd[1] + pw * mt.ks[1];
-          p2 *= ap * mt.kd[2] + pw * mt.ks[2];
+        // one photon per step here: this path calls pow (specular term, Gauss filter), and a
+        // group of photons held across those calls would cost the whole kernel registers
+        const V E = ld3(Q.sh.ex);
+        for (int s = 0; s < num; s++) {
+          uint32_t slot = slot_at(s);
+          float4 p = cpos.get(slot);
+          uint32_t e = crgbe[slot];
+          double ix, iy, iz;
+          lut_dir(a, __float_as_uint(p.w) & 0xffffu, ix, iy, iz);
+          double d2 = (double)metric(qp.x, qp.y, qp.z, p);
+          double perp = Q.perp(ix, iy, iz);
+          if (Q.wrong_side(perp)) continue;
+          C3 t;
+          Q.general_term(a, E, ix, iy, iz, perp, e, d2, t, tw);
+          o = o + t;
         }
-        if (a.filter == 1) {
-          double f = (1.0 - c1 * sqrt(d2));
-          p0 *= f; p1 *= f; p2 *= f;
-        } else if (a.filter == 2) {
-          double w = (1.0 - (1.0 - pow_call(c1, c2 * d2)) / (1.0 - c1));
-          p0 *= w; p1 *= w; p2 *= w;
-          tw += w;
-        }
-        o0 += p0; o1 += p1; o2 += p2;
       }
-      }
-      }
-      bool ok = true;
-      if (a.filter == 0 && maxd2 > 0) {
-        double den = kPi * maxd2;
-        o0 /= den; o1 /= den; o2 /= den;
-      } else if (a.filter == 1 && maxd2 > 0) {
-        double den = (1.0 - 2.0 / 3.0 / a.fk) * kPi * maxd2;
-        o0 /= den; o1 /= den; o2 /= den;
-      } else if (a.filter == 2 && tw > 0 && maxd2 > 0) {
-        double scl = a.fa * (num / tw) / (kPi * maxd2);
-        o0 *= scl; o1 *= scl; o2 *= scl;
-      } else {
-        ok = false;
-      }
-      if (ok) {
-        o0 *= sh.w[0]; o1 *= sh.w[1]; o2 *= sh.w[2];
-      } else {
-        o0 = o1 = o2 = 0;
-      }
+      est_finish(a, a.filter, Q.sh, num, maxd2, tw, o);
     }
   }
-  a.out[3 * qi] = o0;
-  a.out[3 * qi + 1] = o1;
-  a.out[3 * qi + 2] = o2;
-  if (a.out_n) a.out_n[qi] = num;
-  if (a.out_maxd2) a.out_maxd2[qi] = (num > 0) ? (float)maxd2 : 0.0f;
+  est_store(a, qi, num, maxd2, o);
 }
 
 // ---- 4b. the estimate of the chunk's queries that share a surface normal and side, on the
@@ -844,20 +742,14 @@ __device__ __forceinline__ void chunk_estimate_shared(const KnnArgs &a, int lane
     for (int i = 0; i < PC; i++) {
       const uint32_t s = (uint32_t)(i * 64 + lane);
       if (s < count) {
-        const double ix = a.lut[3 * cw[i]], iy = a.lut[3 * cw[i] + 1], iz = a.lut[3 * cw[i] + 2];
+        double ix, iy, iz;
+        lut_dir(a, cw[i], ix, iy, iz);
         const double perp = g0 * ix + g1 * iy + g2 * iz;
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-        const uint32_t e = ce[i], ee = e >> 24;
-        if (!((gs == 2u && perp < 0) || (gs == 1u && perp > 0)) && ee) {
-          const double inv = ldexp(1.0, (int)ee - 128 - 8), ap = fabs(perp);
-          p0 = (double)(e & 255u) * inv;
-          p1 = (double)((e >> 8) & 255u) * inv;
-          p2 = (double)((e >> 16) & 255u) * inv;
-          p0 *= ap; p1 *= ap; p2 *= ap;
-        }
-        tp[s] = p0;
-        tp[CAPC + s] = p1;
-        tp[2 * CAPC + s] = p2;
+        C3 p = rgb(0.0, 0.0, 0.0);
+        if (!wrong_side(gs, perp) && (ce[i] >> 24)) p = disk_term(perp, ce[i]);
+        tp[s] = p.r;
+        tp[CAPC + s] = p.g;
+        tp[2 * CAPC + s] = p.b;
       }
     }
     __syncthreads();
@@ -886,20 +778,9 @@ __device__ __forceinline__ void chunk_estimate_shared(const KnnArgs &a, int lane
     const int K = a.K;
     double maxd2 = (num < K) ? a.rmax * a.rmax : (double)km;
     if (num == K && maxd2 < kEps) maxd2 = kEps;
-    o0 *= mt->kd[0]; o1 *= mt->kd[1]; o2 *= mt->kd[2];
-    if (maxd2 > 0) {
-      const double den = kPi * maxd2;
-      o0 /= den; o1 /= den; o2 /= den;
-      const QShade &sh = a.qshade[qi];
-      o0 *= sh.w[0]; o1 *= sh.w[1]; o2 *= sh.w[2];
-    } else {
-      o0 = o1 = o2 = 0.0;
-    }
-    a.out[3 * qi] = o0;
-    a.out[3 * qi + 1] = o1;
-    a.out[3 * qi + 2] = o2;
-    if (a.out_n) a.out_n[qi] = num;
-    if (a.out_maxd2) a.out_maxd2[qi] = (float)maxd2;
+    C3 o = rgb(o0, o1, o2) * ldc(mt->kd);
+    est_finish(a, 0, a.qshade[qi], num, maxd2, 0.0, o);
+    est_store(a, qi, num, maxd2, o);
   }
 }
 

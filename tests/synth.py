@@ -41,3 +41,17 @@ def queries(n, seed=1, box=1.1, k=50, r=2.5, filt=0, spec=False):
     q["k"] = k
     q["filter"] = filt
     return q
+
+
+def clustered_queries(n, seed, k, r, filt):
+    """Dense queries on one face (the regime the chunk kernel is built for): 64 consecutive
+    Morton-sorted queries span much less than a K-neighbourhood."""
+    q = queries(n, seed=seed, k=k, r=r, filt=filt, spec=True)
+    rng = np.random.default_rng(seed)
+    pts = np.zeros((n, 3))
+    pts[:, 0] = 0.4 + rng.random(n) * 0.2
+    pts[:, 1] = 0.0
+    pts[:, 2] = 0.5 + rng.random(n) * 0.2
+    q["point"] = pts
+    q["normal"] = np.tile([0.0, 1.0, 0.0], (n, 1))
+    return q

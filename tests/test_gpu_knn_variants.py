@@ -23,6 +23,7 @@ import gi_amd
 import oracle_lib
 import synth
 from gi_amd import GLOBAL, DISK, CONE
+from synth import clustered_queries
 
 pytestmark = pytest.mark.gpu
 
@@ -105,20 +106,6 @@ def test_variant_estimate(env, filt, k, r):
     np.testing.assert_array_equal(gn, on)
     np.testing.assert_array_equal(gm, om)
     np.testing.assert_allclose(g, o, rtol=1e-10, atol=1e-300)
-
-
-def clustered_queries(n, seed, k, r, filt):
-    """Dense queries on one face (the regime the chunk kernel is built for): 64 consecutive
-    Morton-sorted queries span much less than a K-neighbourhood."""
-    q = synth.queries(n, seed=seed, k=k, r=r, filt=filt, spec=True)
-    rng = np.random.default_rng(seed)
-    pts = np.zeros((n, 3))
-    pts[:, 0] = 0.4 + rng.random(n) * 0.2
-    pts[:, 1] = 0.0
-    pts[:, 2] = 0.5 + rng.random(n) * 0.2
-    q["point"] = pts
-    q["normal"] = np.tile([0.0, 1.0, 0.0], (n, 1))
-    return q
 
 
 @pytest.mark.parametrize("env", VARIANTS, ids=lambda e: "-".join(f"{k[3:]}{v}" for k, v in e.items()))

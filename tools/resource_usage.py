@@ -20,4 +20,4 @@ for line in out.splitlines():
         k, v = t.split(":", 1)
         cur[k.strip()] = v.strip()
 for r in rows:
-    print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("AGPRs","0"):>3} agpr  spill v{r.get("VGPRs Spill","?"):>4} s{r.get("SGPRs Spill","?"):>4}  lds {r.get("LDS Size [bytes/block]","?"):>6}  occ {r.get("Occupancy [waves/SIMD]","?"):>2}  {r["name"][:110]}')
+    print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("AGPRs","0"):>3} agpr {r.get("TotalSGPRs","?"):>4} sgpr  spill v{r.get("VGPRs Spill","?"):>4} s{r.get("SGPRs Spill","?"):>4}  lds {r.get("LDS Size [bytes/block]","?"):>6}  occ {r.get("Occupancy [waves/SIMD]","?"):>2}  {r["name"][:110]}')
