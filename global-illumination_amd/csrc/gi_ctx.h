@@ -75,11 +75,11 @@ struct Rccl {
 };
 extern Rccl g_rccl;
 
-// The queries a chunk k-NN pass hands on (gi_knn_chunk.hip to_fallback): FB_QS stripes of query
-// ids with their fill counters, and the same ids compacted (dense[n] = their number, n the
-// pass's queries).
+// The queries a chunk k-NN pass hands on (gi_knn_chunk.hip to_fallback): 64 entries of query ids
+// per chunk with the chunks' fill counts (and their scan), and the same ids compacted in chunk
+// order (dense[n] = their number, n the pass's queries).
 struct FbList {
-  DBuf list, count, dense;
+  DBuf list, count, off, tmp, dense;
 };
 
 // Execution state of one photon map's k-NN launches (stream, timing events). One per map, so the

@@ -1,6 +1,6 @@
 // gi_frames.cpp -- what works on finished frames and has no counterpart in the reference:
-// feature planes and the denoisers, radiance frames, the accumulator with its adaptive passes
-// and reprojection, tone mapping.
+// feature planes and the denoisers, radiance frames, the accumulator with its state calls, its
+// adaptive passes and reprojection, tone mapping.
 #include <cmath>
 #include <functional>
 #include "gi_ctx.h"
@@ -384,6 +384,158 @@ int gi_accum_get_counts(gi_ctx *c, int64_t *counts, int64_t *total) {
   }
   if (total) return count_stats(c, nullptr, total);
   return GI_OK;
+}
+
+// ---- accumulator state (gi.h "accumulator state"; accum_fold_states_kernel) -----------------
+static bool any_negative(const int64_t *counts, size_t npix) {
+  for (size_t p = 0; p < npix; p++)
+    if (counts[p] < 0) return true;
+  return false;
+}
+
+// nstates packed states in device memory of c's device folded into the accumulator, in order
+static int fold_states(gi_ctx *c, int nstates, const void *packed, int64_t stride, double *kernel_ms) {
+  FoldArgs a;
+  memset(&a, 0, sizeof a);
+  a.npix = (int64_t)c->acc_w * c->acc_h;
+  a.nstates = nstates;
+  a.stride_bytes = stride;
+  a.states = (const uint8_t *)packed;
+  a.acc = c->res.acc.as<double>();
+  a.counts = c->res.acc_cnt.as<int64_t>();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+      hipEventDestroy(e0);
+      return fail(c, GI_ERR_HIP, "accumulator merge: hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, c->stream);
+  }
+  launch_accum_fold_states(a, c->stream);
+  hipError_t le = hipGetLastError();
+  if (kernel_ms) (void)hipEventRecord(e1, c->stream);
+  if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
+  if (kernel_ms) {
+    float ms = 0.f;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    *kernel_ms = ms;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  HIPCHK(c, le);
+  c->acc_uniform = false;  // every pixel under its own count from here on
+  return GI_OK;
+}
+
+int gi_accum_export(gi_ctx *c, double *state, int64_t *counts) {
+  if (!c) return GI_ERR_ARG;
+  if (int rc = check_accum(c)) return rc;
+  if (!state && !counts) return fail(c, GI_ERR_ARG, "null state buffers");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  if (state) HIPCHK(c, hipMemcpyAsync(state, c->res.acc.p, npix * 48, hipMemcpyDeviceToHost, c->stream));
+  if (counts)
+    HIPCHK(c, hipMemcpyAsync(counts, c->res.acc_cnt.p, npix * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+int gi_accum_import(gi_ctx *c, int w, int h, const double *state, const int64_t *counts) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(c, GI_ERR_ARG, "bad image size");
+  if (!state || !counts) return fail(c, GI_ERR_ARG, "null state buffers");
+  const size_t npix = (size_t)w * h;
+  if (any_negative(counts, npix)) return fail(c, GI_ERR_ARG, "accumulator state: negative sample count");
+  DeviceScope dev(c->device);
+  c->acc_valid = false;
+  HIPCHK(c, c->res.acc.ensure(npix * 48));
+  HIPCHK(c, c->res.acc_cnt.ensure(npix * 8));
+  if (c->res.acc2.p) {  // as gi_accum_reset
+    HIPCHK(c, c->res.acc2.ensure(npix * 48));
+    HIPCHK(c, c->res.acc2_cnt.ensure(npix * 8));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->res.acc.p, state, npix * 48, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->res.acc_cnt.p, counts, npix * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->acc_w = w;
+  c->acc_h = h;
+  c->acc_n = 0;
+  c->acc_uniform = false;  // every pixel under its own count
+  c->acc_valid = true;
+  return GI_OK;
+}
+
+int gi_accum_merge(gi_ctx *c, int w, int h, const double *state, const int64_t *counts) {
+  if (!c) return GI_ERR_ARG;
+  if (int rc = check_accum(c)) return rc;
+  if (w != c->acc_w || h != c->acc_h)
+    return fail(c, GI_ERR_ARG, "accumulator state: not the accumulator's size");
+  if (!state || !counts) return fail(c, GI_ERR_ARG, "null state buffers");
+  const size_t npix = (size_t)w * h;
+  if (any_negative(counts, npix)) return fail(c, GI_ERR_ARG, "accumulator state: negative sample count");
+  DeviceScope dev(c->device);
+  DBuf packed;
+  HIPCHK(c, packed.ensure(npix * 56));
+  HIPCHK(c, hipMemcpyAsync(packed.p, state, npix * 48, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(packed.as<uint8_t>() + npix * 48, counts, npix * 8, hipMemcpyHostToDevice,
+                           c->stream));
+  return fold_states(c, 1, packed.p, (int64_t)npix * 56, nullptr);
+}
+
+int gi_accum_export_packed(gi_ctx *c, void *packed, int64_t cap, int64_t *bytes) {
+  if (!c) return GI_ERR_ARG;
+  if (int rc = check_accum(c)) return rc;
+  if (!packed && !bytes) return fail(c, GI_ERR_ARG, "null state buffers");
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  if (bytes) *bytes = (int64_t)npix * 56;
+  if (!packed) return GI_OK;
+  if (cap < (int64_t)npix * 56) return fail(c, GI_ERR_ARG, "packed buffer smaller than the state");
+  DeviceScope dev(c->device);
+  HIPCHK(c, hipMemcpyAsync(packed, c->res.acc.p, npix * 48, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((uint8_t *)packed + npix * 48, c->res.acc_cnt.p, npix * 8,
+                           hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+int gi_accum_merge_packed(gi_ctx *c, int nstates, const void *packed, int64_t stride, double *kernel_ms) {
+  if (!c) return GI_ERR_ARG;
+  if (int rc = check_accum(c)) return rc;
+  if (!packed || nstates < 1) return fail(c, GI_ERR_ARG, "accumulator merge: no states");
+  if ((uintptr_t)packed % 8) return fail(c, GI_ERR_ARG, "accumulator merge: states not 8-byte aligned");
+  if (stride < (int64_t)c->acc_w * c->acc_h * 56 || stride % 8)
+    return fail(c, GI_ERR_ARG, "accumulator merge: stride below the state's size or not a multiple of 8");
+  DeviceScope dev(c->device);
+  return fold_states(c, nstates, packed, stride, kernel_ms);
+}
+
+int gi_accum_merge_from(gi_ctx *c, gi_ctx *src, double *kernel_ms) {
+  if (!c || !src) return GI_ERR_ARG;
+  if (c == src) return fail(c, GI_ERR_ARG, "accumulator merge: source is the destination");
+  if (!src->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "the accumulator is for one-device contexts");
+  if (int rc = check_accum(c)) return rc;
+  if (!src->acc_valid) return fail(c, GI_ERR_STATE, "the source has no accumulator (gi_accum_reset)");
+  if (src->acc_w != c->acc_w || src->acc_h != c->acc_h)
+    return fail(c, GI_ERR_ARG, "accumulator state: not the accumulator's size");
+  DeviceScope dev(c->device);
+  const size_t npix = (size_t)c->acc_w * c->acc_h;
+  DBuf packed;
+  HIPCHK(c, packed.ensure(npix * 56));
+  uint8_t *cnt = packed.as<uint8_t>() + npix * 48;
+  // every accumulator call ends synchronised, so the source's planes are complete
+  if (src->device == c->device) {
+    HIPCHK(c, hipMemcpyAsync(packed.p, src->res.acc.p, npix * 48, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt, src->res.acc_cnt.p, npix * 8, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyPeerAsync(packed.p, c->device, src->res.acc.p, src->device, npix * 48, c->stream));
+    HIPCHK(c, hipMemcpyPeerAsync(cnt, c->device, src->res.acc_cnt.p, src->device, npix * 8, c->stream));
+  }
+  return fold_states(c, 1, packed.p, (int64_t)npix * 56, kernel_ms);
 }
 
 // ---- adaptive passes (gi.h "adaptive passes"; tile_error_kernel, tile_select_kernel) ----------

@@ -144,19 +144,17 @@ static int knn_end(gi_ctx *c, MapExec &X, double *ms) {
 }
 
 // Makes F ready for what a chunk pass over nq queries hands on and points the pass's arguments
-// at it. Striped list (gi_knn_chunk.hip to_fallback): block b -> stripe b % FB_QS, at most 64
-// queries per chunk, ceil(chunks / grid) chunks per block.
+// at it. Per-chunk list (gi_knn_chunk.hip to_fallback): chunk c's queries at [64 c, 64 c + count[c]),
+// so the compacted list is in chunk order in every launch.
 static int fb_prepare(gi_ctx *c, MapExec &X, FbList &F, int64_t nq, KnnArgs &k) {
-  int64_t chunks = (nq + 63) / 64;
-  int64_t grid = knn_chunk_grid(nq);
-  uint32_t cap_s = (uint32_t)(64 * ((chunks + grid - 1) / grid) * ((grid + FB_QS - 1) / FB_QS));
-  HIPCHK(c, F.list.ensure((size_t)FB_QS * cap_s * 4));
+  const int64_t chunks = (nq + 63) / 64;
+  HIPCHK(c, F.list.ensure((size_t)chunks * 64 * 4));
   HIPCHK(c, F.dense.ensure((size_t)nq * 4 + 4));
-  HIPCHK(c, F.count.ensure(FB_QS * 32 * 4));
-  HIPCHK(c, hipMemsetAsync(F.count.p, 0, FB_QS * 32 * 4, X.st));
+  HIPCHK(c, F.count.ensure((size_t)(chunks + 1) * 4));
+  HIPCHK(c, F.off.ensure((size_t)(chunks + 1) * 4));
+  HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)(chunks + 1) * 4, X.st));
   k.fb_list = F.list.as<uint32_t>();
   k.fb_count = F.count.as<uint32_t>();
-  k.fb_cap_s = cap_s;
   return GI_OK;
 }
 
@@ -165,8 +163,13 @@ static int fb_prepare(gi_ctx *c, MapExec &X, FbList &F, int64_t nq, KnnArgs &k) 
 static int fb_collect(gi_ctx *c, MapExec &X, FbList &F, const KnnArgs &k, int64_t nq,
                       hipEvent_t ev, uint32_t *n) {
   uint32_t *dense = F.dense.as<uint32_t>();
-  launch_fb_compact(k.fb_list, k.fb_count, k.fb_cap_s, dense, dense + nq, X.st);
-  HIPCHK(c, hipGetLastError());
+  const int64_t chunks = (nq + 63) / 64;
+  size_t tb = 0;
+  HIPCHK(c, launch_fb_compact(k.fb_list, k.fb_count, chunks, F.off.as<uint32_t>(), nullptr, tb, dense,
+                              dense + nq, X.st));
+  HIPCHK(c, F.tmp.ensure(tb + 256));
+  HIPCHK(c, launch_fb_compact(k.fb_list, k.fb_count, chunks, F.off.as<uint32_t>(), F.tmp.p, tb, dense,
+                              dense + nq, X.st));
   if (ev) HIPCHK(c, hipEventRecord(ev, X.st));
   HIPCHK(c, hipMemcpyAsync(n, dense + nq, 4, hipMemcpyDeviceToHost, X.st));
   HIPCHK(c, hipStreamSynchronize(X.st));
@@ -382,7 +385,8 @@ struct ListRows {
 };
 
 static int knn_list(gi_ctx *c, int mi, const float4 *qpos, const QShade *qshade, int64_t nq,
-             double *out, double *ms, const ListRows *rows = nullptr) {
+             double *out, double *ms, const ListRows *rows = nullptr, uint32_t qbase = 0,
+             const uint32_t *app_order = nullptr) {
   MapExec &X = c->mx[mi];
   MapScratch &XS = c->s.map[mi];
   KnnArgs k = knn_args(c, mi);
@@ -408,14 +412,14 @@ static int knn_list(gi_ctx *c, int mi, const float4 *qpos, const QShade *qshade,
       int64_t nv = 0;
       HIPCHK(c, curve_order_rows(qpos, rows->nprim, rows->qmask, rows->trows, rows->qbase, nq,
                                  c->sbmin, c->sbmax, XS.sorter, &perm, &nv, X.st,
-                                 c->surf_key));
+                                 c->surf_key, app_order));
       nq = nv;
       k.nq = nv;
       if (nv == 0) return GI_OK;
     } else {
       int64_t nv = 0;
       HIPCHK(c, morton_order_valid(qpos, nq, c->sbmin, c->sbmax, XS.sorter, &perm, &nv, X.st,
-                                   c->key_bits[mi], c->surf_key_c));
+                                   c->key_bits[mi], c->surf_key_c, qbase, app_order));
       nq = nv;
       k.nq = nv;
       if (nv == 0) return GI_OK;
@@ -707,7 +711,8 @@ static int estimates(gi_ctx *c, RenderArgs &a, Batch &B) {
     ListRows lr{B.nprim, a.ind_qmask, (int64_t)(B.tind / 64), B.qbase[0]};
     const bool use_rows = l == 0 && a.ind_qmask && (a.total_ind > 0 || B.tind == 0);
     int rc = knn_list(c, l, a.qpos[l], a.qshade[l], nq[l], c->s.qout[l].as<double>(),
-                      B.timed ? &B.knn_ms[l] : nullptr, use_rows ? &lr : nullptr);
+                      B.timed ? &B.knn_ms[l] : nullptr, use_rows ? &lr : nullptr, B.qbase[l],
+                      a.sslot[l]);
     if (rc) return rc;
   }
   return GI_OK;
@@ -846,8 +851,9 @@ static int render_pixels(gi_ctx *c, int aa, int w, int h, const std::vector<int3
     }
     if (!rc) rc = path_setup(c, a, B);
     if (!rc) rc = path_pass(c, a, B);
-    if (!rc) rc = estimates(c, a, B);
+    // (the appends' key order first: it also fixes their place in the k-NN launch order)
     if (!rc) rc = order_appends(c, a, B);
+    if (!rc) rc = estimates(c, a, B);
     if (!rc) rc = reduce(c, a, B);
     if (rc) return rc;
     for (int l = 0; l < 2; l++) {

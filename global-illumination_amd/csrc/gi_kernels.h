@@ -66,8 +66,6 @@ struct IndCont {
 constexpr int IND_QS = 64;
 // IndCont::g of an empty entry of the dense Monte Carlo sub-path queue (mc_persist_kernel)
 constexpr uint32_t IND_EMPTY = 0xffffffffu;
-// chunk k-NN fallback list stripes: block b appends to stripe b % FB_QS
-constexpr int FB_QS = 64;
 
 // A Monte Carlo path between two bounces of the breadth-first schedule (mc_wave_begin_kernel /
 // mc_wave_step_kernel, GI_MC_WAVE): MonteCarlo_PathTrace's loop state (McLoop) and what the
@@ -375,8 +373,8 @@ struct KnnArgs {
   float *list_d2;          //   and their d2; -1 past list_n[q]
   int32_t *list_n;
   uint32_t *fb_list;       // chunk kernel: queries (original slots) handed to the fallback,
-  uint32_t *fb_count;      // FB_QS stripes of fb_cap_s entries; fill of stripe s at [s * 32]
-  uint32_t fb_cap_s;
+  uint32_t *fb_count;      // 64 entries per chunk of the pass, chunk c's at [64 c]; fb_count[c] of
+                           // them are filled (zeroed by the host before the pass)
   float *gheap_d2;         // global heap scratch (K > 64)
   int32_t *gheap_idx;
   unsigned long long *stats;
@@ -429,9 +427,11 @@ void launch_path(const RenderArgs &a, hipStream_t st, hipStream_t st2 = nullptr,
                  const McWave *mw = nullptr);
 // float4 queries {x, y, z, 0} at the photons of a map (KNN_MODE_DK input)
 void launch_photon_queries(const float *pos4, int64_t n, float4 *q, hipStream_t st);
-// dense copy of the striped chunk fallback list; total length to *total
-void launch_fb_compact(const uint32_t *list, const uint32_t *count, uint32_t cap_s, uint32_t *dense,
-                       uint32_t *total, hipStream_t st);  // slot0 + indirect + Monte Carlo
+// dense copy of the per-chunk fallback list in chunk order; total length to *total. off: chunks + 1
+// words; tmp == nullptr only reports the scan's scratch size in tmp_bytes
+hipError_t launch_fb_compact(const uint32_t *list, uint32_t *count, int64_t chunks, uint32_t *off,
+                             void *tmp, size_t &tmp_bytes, uint32_t *dense, uint32_t *total,
+                             hipStream_t st);  // slot0 + indirect + Monte Carlo
 void launch_reduce(const RenderArgs &a, hipStream_t st);
 void launch_owner_table(const uint32_t *off, int64_t n, uint32_t *tab, hipStream_t st);
 void launch_ind_tiles(const uint32_t *nind, int64_t nprim, uint32_t *rows, hipStream_t st);

@@ -21,6 +21,7 @@
 // capacity (Morton jumps, sparse regions) go to a fallback list, and the per-lane kernel
 // (gi_knn.hip) answers those queries.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <cstdlib>
 #include <type_traits>
 #include "gi_device.h"
@@ -584,16 +585,15 @@ __device__ __forceinline__ float query_lim2(const KnnArgs &a, const ChunkGeom &G
 
 // hand the wave's valid queries to the per-lane fallback kernel
 __device__ __forceinline__ void to_fallback(const KnnArgs &a, uint64_t vmask, bool valid, int64_t qi,
-                                            int lane) {
-  // one atomic per wave, on the block's stripe (a single counter would serialise the waves)
-  uint32_t nv = (uint32_t)__popcll(vmask);
-  const uint32_t s = blockIdx.x & (FB_QS - 1);
-  uint32_t base = 0;
-  if (lane == 0) base = atomicAdd(&a.fb_count[s * 32], nv);
-  base = (uint32_t)__shfl((int)base, 0, 64);
+                                            int lane, int64_t chunk, uint32_t &fbn) {
+  // the chunk's own 64 entries, behind what the chunk handed on before (fbn): the list's order is
+  // the chunks' order whatever order the blocks run in, so the next pass cuts the same chunks from
+  // it in every launch (a fill counter shared by blocks ordered it by arrival)
   if (valid)
-    a.fb_list[(size_t)s * a.fb_cap_s + base + (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull))] =
+    a.fb_list[(size_t)chunk * 64 + fbn + (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull))] =
         (uint32_t)qi;
+  fbn += (uint32_t)__popcll(vmask);
+  if (lane == 0) a.fb_count[chunk] = fbn;
 }
 
 // ---- 4. the estimate of one query from LDS-staged photons (slot_at(s) = s-th kept slot).
@@ -923,6 +923,7 @@ void knn_chunk_lane_kernel(KnnArgs a) {
     // Morton-adjacent queries (smaller boxes gather fewer photons); what still overflows goes
     // to the per-lane kernel. Lanes outside the current group idle through its select.
     uint64_t pending = vmask;
+    uint32_t fbn = 0;  // queries of this chunk handed on so far
     for (int sub = 64; sub >= minsub && pending; sub >>= 1) {
     for (int g0 = 0; g0 < 64; g0 += sub) {
     const uint64_t gm = (sub == 64) ? ~0ull : (((1ull << sub) - 1ull) << g0);
@@ -1037,7 +1038,7 @@ void knn_chunk_lane_kernel(KnnArgs a) {
     const bool fb = mode == 1 || mode == 3;
     uint64_t fbm = __ballot(fb);
     if (fbm) {
-      to_fallback(a, fbm, fb, qi, lane);
+      to_fallback(a, fbm, fb, qi, lane, chunk, fbn);
       if (P.on) P.c[9] += (uint64_t)__popcll(fbm);
     }
     const bool col = act && !fb && !(a.dbg & 4);
@@ -1131,7 +1132,7 @@ void knn_chunk_lane_kernel(KnnArgs a) {
     }
     }
     if (pending) {
-      to_fallback(a, pending, valid && ((pending >> lane) & 1ull), qi, lane);
+      to_fallback(a, pending, valid && ((pending >> lane) & 1ull), qi, lane, chunk, fbn);
     }
   }
   chunk_flush_stats(a, P, st_q, st_found, st_vis);
@@ -1181,6 +1182,7 @@ void knn_chunk_big_kernel(KnnArgs a) {
     // an overflowing chunk is retried as halves, quarters, ... down to minsub queries (the
     // query-per-wave fallback costs several times a lane-select query even at 1/8 occupancy)
     uint64_t pending = vmask;
+    uint32_t fbn = 0;  // queries of this chunk handed on so far
     for (int sub = 64; sub >= minsub && pending; sub >>= 1) {
     for (int g0 = 0; g0 < 64; g0 += sub) {
     const uint64_t gm = (sub == 64) ? ~0ull : (((1ull << sub) - 1ull) << g0);
@@ -1270,7 +1272,7 @@ void knn_chunk_big_kernel(KnnArgs a) {
     const bool fb = mode == 1 || mode == 3;
     uint64_t fbm = __ballot(fb);
     if (fbm) {
-      to_fallback(a, fbm, fb, qi, lane);
+      to_fallback(a, fbm, fb, qi, lane, chunk, fbn);
       if (P.on) P.c[9] += (uint64_t)__popcll(fbm);
     }
     const bool col = act && !fb;
@@ -1370,28 +1372,31 @@ void knn_chunk_big_kernel(KnnArgs a) {
     P.lap(3);
     }
     }
-    if (pending) to_fallback(a, pending, valid && ((pending >> lane) & 1ull), qi, lane);
+    if (pending) to_fallback(a, pending, valid && ((pending >> lane) & 1ull), qi, lane, chunk, fbn);
   }
   chunk_flush_stats(a, P, st_q, st_found, st_vis);
 }
 
-// dense copy of the striped fallback list: block b copies stripe b % FB_QS after the fills of
-// the stripes before it
+// dense copy of the per-chunk fallback list: one thread per chunk copies its count[c] <= 64 entries
+// behind those of the chunks before it (off: the exclusive scan of count, the total at off[chunks])
 __global__ __launch_bounds__(256) void fb_compact_kernel(const uint32_t *list, const uint32_t *count,
-                                                         uint32_t cap_s, uint32_t *dense,
-                                                         uint32_t *total) {
-  const uint32_t s = blockIdx.x % FB_QS, part = blockIdx.x / FB_QS, parts = gridDim.x / FB_QS;
-  uint32_t off = 0;
-  for (uint32_t i = 0; i < s; i++) off += count[i * 32];
-  const uint32_t n = count[s * 32];
-  for (uint32_t idx = part * blockDim.x + threadIdx.x; idx < n; idx += parts * blockDim.x)
-    dense[off + idx] = list[(size_t)s * cap_s + idx];
-  if (s == FB_QS - 1 && part == 0 && threadIdx.x == 0) *total = off + n;
+                                                         const uint32_t *off, int64_t chunks,
+                                                         uint32_t *dense, uint32_t *total) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0) *total = off[chunks];
+  if (c >= chunks) return;
+  const uint32_t n = count[c], o = off[c];
+  for (uint32_t i = 0; i < n; i++) dense[o + i] = list[(size_t)c * 64 + i];
 }
 
-void launch_fb_compact(const uint32_t *list, const uint32_t *count, uint32_t cap_s, uint32_t *dense,
-                       uint32_t *total, hipStream_t st) {
-  fb_compact_kernel<<<FB_QS * 8, 256, 0, st>>>(list, count, cap_s, dense, total);
+hipError_t launch_fb_compact(const uint32_t *list, uint32_t *count, int64_t chunks, uint32_t *off,
+                             void *tmp, size_t &tmp_bytes, uint32_t *dense, uint32_t *total,
+                             hipStream_t st) {
+  // count[chunks] is the scan's extra element (the host zeroes it with the counts)
+  hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, count, off, (int)(chunks + 1), st);
+  if (e != hipSuccess || !tmp) return e;
+  fb_compact_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, st>>>(list, count, off, chunks, dense, total);
+  return hipGetLastError();
 }
 
 // chunk kernels' grid: one 64-query chunk per block, at most 2^17 blocks (grid-stride beyond)

@@ -115,6 +115,21 @@ inline int64_t reproject_waves(int w, int h) {
          REPROJECT_BY;
 }
 
+// accum_fold_states_kernel (gi.h "accumulator state"): nstates packed states, state s at states +
+// s * stride_bytes ({mu, A} plane of npix * 48 B, then the count plane of npix * 8 B), folded into
+// the accumulator in the order s = 0 .. nstates - 1. One thread per pixel, FOLD_BLOCK consecutive
+// pixels per block; the running value stays in registers, so the accumulator is read once and
+// written once and each state is read once. stride_bytes is a multiple of 8.
+constexpr int FOLD_BLOCK = 256;
+struct FoldArgs {
+  int64_t npix;
+  int32_t nstates;
+  int64_t stride_bytes;
+  const uint8_t *states;    // [nstates * stride_bytes]
+  double *acc;              // [npix * 6]
+  int64_t *counts;          // [npix]
+};
+
 // tonemap_kernel: one thread per channel value
 struct TonemapArgs {
   int64_t nval;             // W * H * 3
@@ -131,6 +146,7 @@ void launch_count_stats(const CountArgs &a, hipStream_t st);
 void launch_tile_error(const TileArgs &a, hipStream_t st);
 void launch_tile_select(const SelectArgs &a, hipStream_t st);
 void launch_accum_reproject(const ReprojectArgs &a, hipStream_t st);
+void launch_accum_fold_states(const FoldArgs &a, hipStream_t st);
 void launch_tonemap(const TonemapArgs &a, hipStream_t st);
 
 }  // namespace gi

@@ -13,6 +13,8 @@
 //   tile_error_kernel        adaptive passes: the same error per tile, one wave per tile
 //   tile_select_kernel       ... and the tile mask (thresholds, 8-neighbour dilation)
 //   accum_reproject_kernel   the accumulator carried into a new camera (tests/reproject_ref.py)
+//   accum_fold_states_kernel exported accumulator states folded into the accumulator, K at a time
+//                            (tests/accum_state_ref.py)
 //   tonemap_kernel           exposure, extended Reinhard curve, clamp
 #include <hip/hip_runtime.h>
 #include "gi_radiance.h"
@@ -298,6 +300,60 @@ __global__ __launch_bounds__(REPROJECT_BX * REPROJECT_BY) void accum_reproject_k
   }
 }
 
+// The records of pixels [p0, p0 + np) of a {mu, A} plane, read as one contiguous run (lane i takes
+// double i of the run, then i + FOLD_BLOCK, ...: 512 B per wave instruction, where a thread that
+// read its own 48-B record would touch 3 KiB per instruction) and handed to their threads through
+// LDS. Every thread of the block calls it.
+__device__ __forceinline__ void fold_stage(const double *plane, int64_t p0, int np, double *x,
+                                           double *r) {
+  const int t = threadIdx.x;
+  const double *run = plane + p0 * 6;
+  __syncthreads();  // x's readers of the stage before are done
+  for (int i = t; i < np * 6; i += FOLD_BLOCK) x[i] = run[i];
+  __syncthreads();
+  if (t < np)
+    for (int c = 0; c < 6; c++) r[c] = x[t * 6 + c];
+}
+
+// gi.h "accumulator state": the fold of b into a per pixel, in accum_merge_kernel's operation order
+// with (S, m, M2) = (n_b, mu_b, A_b); an empty b leaves a as it is, an empty a takes b as it is.
+__global__ __launch_bounds__(FOLD_BLOCK) void accum_fold_states_kernel(FoldArgs a) {
+  __shared__ double x[FOLD_BLOCK * 6];
+  const int t = threadIdx.x;
+  const int64_t p0 = (int64_t)blockIdx.x * FOLD_BLOCK;
+  const int64_t left = a.npix - p0;
+  const int np = left < FOLD_BLOCK ? (int)left : FOLD_BLOCK;
+  const bool live = t < np;
+  double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, f[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  fold_stage(a.acc, p0, np, x, g);
+  int64_t n = live ? a.counts[p0 + t] : 0;
+  for (int s = 0; s < a.nstates; s++) {
+    const uint8_t *state = a.states + (int64_t)s * a.stride_bytes;
+    fold_stage(reinterpret_cast<const double *>(state), p0, np, x, f);
+    const int64_t nb = live ? reinterpret_cast<const int64_t *>(state + a.npix * 48)[p0 + t] : 0;
+    if (nb != 0 && n == 0) {
+      for (int c = 0; c < 6; c++) g[c] = f[c];
+      n = nb;
+    } else if (nb != 0) {
+      const double Nb = (double)nb, N1 = (double)(n + nb), NS = (double)n * Nb;
+      for (int c = 0; c < 3; c++) {
+        const double d = f[c] - g[c];
+        g[c] = g[c] + (d * Nb) / N1;
+        g[3 + c] = (g[3 + c] + f[3 + c]) + ((d * d) * NS) / N1;
+      }
+      n = n + nb;
+    }
+  }
+  __syncthreads();
+  if (live) {
+    for (int c = 0; c < 6; c++) x[t * 6 + c] = g[c];
+    a.counts[p0 + t] = n;
+  }
+  __syncthreads();
+  double *run = a.acc + p0 * 6;
+  for (int i = t; i < np * 6; i += FOLD_BLOCK) run[i] = x[i];
+}
+
 __global__ __launch_bounds__(256) void tonemap_kernel(TonemapArgs a) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.nval) return;
@@ -335,6 +391,10 @@ void launch_accum_reproject(const ReprojectArgs &a, hipStream_t st) {
   if (a.W <= 0 || a.H <= 0) return;
   const unsigned grid = (unsigned)(reproject_waves(a.W, a.H) / REPROJECT_BY);  // row-major blocks
   accum_reproject_kernel<<<grid, dim3(REPROJECT_BX, REPROJECT_BY), 0, st>>>(a);
+}
+void launch_accum_fold_states(const FoldArgs &a, hipStream_t st) {
+  if (a.npix > 0 && a.nstates > 0)
+    accum_fold_states_kernel<<<nblk(a.npix, FOLD_BLOCK), FOLD_BLOCK, 0, st>>>(a);
 }
 void launch_tonemap(const TonemapArgs &a, hipStream_t st) {
   if (a.nval > 0) tonemap_kernel<<<nblk(a.nval, 256), 256, 0, st>>>(a);

@@ -19,7 +19,12 @@ hipError_t morton_order(const float4 *q, int64_t n, const float bmin[3], const f
 // surface keys with 16-bit in-plane cells (gi_sort.hip surf64_valid_kernel)
 hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], const float bmax[3],
                               SortScratch &s, uint32_t **perm_out, int64_t *nvalid, hipStream_t st,
-                              int key_bits = 10, bool surf = false);
+                              int key_bits = 10, bool surf = false, uint32_t qbase = 0,
+                              const uint32_t *app_order = nullptr);
+// qbase, app_order (both sorts; null: slot order): the slots [qbase, n) are a render list's Monte
+// Carlo appends, which take their slots in arrival order; they enter the sort in the order
+// app_order gives (key_order's sslots of their own keys, relative to qbase), so that queries with
+// equal sort keys come out in the same order in every launch
 // The global list's launch order built from its slot layout instead of a sort over every slot:
 // primary slots [0, nprim) (validity read from q), then the tiled indirect slots [nprim,
 // nprim + 64 trows) whose row masks qmask[r] mark the entries holding a query (the reduction's
@@ -32,7 +37,7 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
 hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmask, int64_t trows,
                             uint32_t qbase, int64_t nq, const float bmin[3], const float bmax[3],
                             SortScratch &s, uint32_t **perm_out, int64_t *nvalid, hipStream_t st,
-                            bool surf = false);
+                            bool surf = false, const uint32_t *app_order = nullptr);
 // key parameters: the 3-D curve's 10-bit cells (origin o, scale s per axis, cmax), or, with surf,
 // the surface key's square 11-bit cells (siso) and 32 depth slabs per axis (sdep)
 struct KeyGeom {

@@ -178,46 +178,57 @@ hipError_t morton_order(const float4 *q, int64_t n, const float bmin[3], const f
   return hipSuccess;
 }
 
+// The slot the sort's entry i stands for: i itself, or for the Monte Carlo appends [qbase, n) of a
+// render list the append of rank i - qbase in the order of the appends' own keys (order: slots
+// relative to qbase). The appends take their slots in arrival order; entered in key order, queries
+// with equal sort keys keep an order that is the same in every launch.
+__device__ __forceinline__ uint32_t list_slot(int64_t i, uint32_t qbase, const uint32_t *order) {
+  return (order && i >= (int64_t)qbase) ? qbase + order[i - (int64_t)qbase] : (uint32_t)i;
+}
+
 // Morton keys of the valid queries (meta != QMETA_NONE) and, for the empty slots, the key 2^30
 // (above every 30-bit code): the stable sort puts the valid queries first, in the order
 // morton_order gives them, and the empty ones after them
 __global__ void morton_valid_kernel(const float4 *q, int64_t n, float ox, float oy, float oz,
                                     float sx, float sy, float sz, float cmax, uint32_t *keys,
-                                    uint32_t *vals) {
+                                    uint32_t *vals, uint32_t qbase, const uint32_t *order) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = q[i];
+  const uint32_t slot = list_slot(i, qbase, order);
+  float4 p = q[slot];
   const bool valid = __float_as_uint(p.w) != 0xffffffffu;  // QMETA_NONE (gi_kernels.h)
   float fx = fminf(fmaxf((p.x - ox) * sx, 0.0f), cmax);
   float fy = fminf(fmaxf((p.y - oy) * sy, 0.0f), cmax);
   float fz = fminf(fmaxf((p.z - oz) * sz, 0.0f), cmax);
   keys[i] = valid ? curve_key10((uint32_t)fx, (uint32_t)fy, (uint32_t)fz) : (1u << 30);
-  vals[i] = (uint32_t)i;
+  vals[i] = slot;
 }
 
 // morton_valid_kernel with B-bit cells (64-bit keys; the empty slots get 2^(3B))
 template <int B>
 __global__ void curve64_valid_kernel(const float4 *q, int64_t n, float ox, float oy, float oz,
                                      float sx, float sy, float sz, float cmax, uint64_t *keys,
-                                     uint32_t *vals) {
+                                     uint32_t *vals, uint32_t qbase, const uint32_t *order) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = q[i];
+  const uint32_t slot = list_slot(i, qbase, order);
+  float4 p = q[slot];
   const bool valid = __float_as_uint(p.w) != 0xffffffffu;  // QMETA_NONE (gi_kernels.h)
   float fx = fminf(fmaxf((p.x - ox) * sx, 0.0f), cmax);
   float fy = fminf(fmaxf((p.y - oy) * sy, 0.0f), cmax);
   float fz = fminf(fmaxf((p.z - oz) * sz, 0.0f), cmax);
   keys[i] = valid ? curve_key64<B>((uint32_t)fx, (uint32_t)fy, (uint32_t)fz) : (1ull << (3 * B));
-  vals[i] = (uint32_t)i;
+  vals[i] = slot;
 }
 // the surface key with B-bit in-plane cells as a 64-bit key (8 + 2B bits: face, slab, 2-D curve;
 // the empty slots get 2^(8 + 2B))
 template <int B>
 __global__ void surf64_valid_kernel(const float4 *q, int64_t n, KeyGeom g, uint64_t *keys,
-                                    uint32_t *vals) {
+                                    uint32_t *vals, uint32_t qbase, const uint32_t *order) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = q[i];
+  const uint32_t slot = list_slot(i, qbase, order);
+  float4 p = q[slot];
   const bool valid = __float_as_uint(p.w) != 0xffffffffu;  // QMETA_NONE (gi_kernels.h)
   uint64_t key = 1ull << (8 + 2 * B);
   if (valid) {
@@ -225,7 +236,7 @@ __global__ void surf64_valid_kernel(const float4 *q, int64_t n, KeyGeom g, uint6
     key = ((uint64_t)c.face << (5 + 2 * B)) | ((uint64_t)c.dep << (2 * B)) | hilbert2<B>(c.cu, c.cv);
   }
   keys[i] = key;
-  vals[i] = (uint32_t)i;
+  vals[i] = slot;
 }
 // first sorted key >= empty (the valid keys sort before the empty slots' key): one wave, 64
 // probes per round
@@ -323,10 +334,10 @@ __global__ __launch_bounds__(256) void row_keys_kernel(const uint64_t *rows, con
   }
 }
 __global__ void append_keys_kernel(const float4 *q, uint32_t qbase, int64_t napp, int64_t ndet,
-                                   KeyGeom g, uint32_t *keys, uint32_t *vals) {
+                                   KeyGeom g, uint32_t *keys, uint32_t *vals, const uint32_t *order) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= napp) return;
-  const uint32_t slot = qbase + (uint32_t)i;
+  const uint32_t slot = list_slot((int64_t)qbase + i, qbase, order);
   keys[ndet + i] = slot_key10(q, slot, g);
   vals[ndet + i] = slot;
 }
@@ -356,7 +367,7 @@ static hipError_t wide_sort(void *tmp, size_t &tb, const uint64_t *k0, uint64_t 
 
 hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], const float bmax[3],
                               SortScratch &s, uint32_t **perm_out, int64_t *nvalid, hipStream_t st,
-                              int key_bits, bool surf) {
+                              int key_bits, bool surf, uint32_t qbase, const uint32_t *app_order) {
   *perm_out = nullptr;
   *nvalid = 0;
   if (n <= 0) return hipSuccess;
@@ -384,7 +395,7 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
     }
     g.siso = emax > 0 ? (float)(1u << B) / emax : 0.0f;
     surf64_valid_kernel<B><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q, n, g, (uint64_t *)s.k0.p,
-                                                                        (uint32_t *)s.v0.p);
+                                                                        (uint32_t *)s.v0.p, qbase, app_order);
     size_t tb = 0;
     e = wide_sort(nullptr, tb, (const uint64_t *)s.k0.p, (uint64_t *)s.k1.p, (const uint32_t *)s.v0.p,
                   (uint32_t *)s.v1.p, n, 8 + 2 * B + 1, st);
@@ -407,7 +418,7 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
 #define CURVE64_CASE(b)                                                                      \
   case b:                                                                                    \
     curve64_valid_kernel<b><<<g, 256, 0, st>>>(q, n, bmin[0], bmin[1], bmin[2], sw[0], sw[1], \
-                                               sw[2], cm, (uint64_t *)s.k0.p, (uint32_t *)s.v0.p); \
+                                               sw[2], cm, (uint64_t *)s.k0.p, (uint32_t *)s.v0.p, qbase, app_order); \
     break;
     switch (B) {
       CURVE64_CASE(11) CURVE64_CASE(12) CURVE64_CASE(13) CURVE64_CASE(14) CURVE64_CASE(15)
@@ -436,7 +447,7 @@ hipError_t morton_order_valid(const float4 *q, int64_t n, const float bmin[3], c
   }
   morton_valid_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
       q, n, bmin[0], bmin[1], bmin[2], sc[0], sc[1], sc[2], cmax, (uint32_t *)s.k0.p,
-      (uint32_t *)s.v0.p);
+      (uint32_t *)s.v0.p, qbase, app_order);
   size_t tb = 0;
   // 31 key bits: the 30-bit code and the empty slots' 2^30 (four 8-bit passes, as for 30 bits)
   e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)s.k0.p, (uint32_t *)s.k1.p,
@@ -491,7 +502,7 @@ hipError_t key_order(const uint64_t *keys, int64_t n, int key_bits, KeySortScrat
 hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmask, int64_t trows,
                             uint32_t qbase, int64_t nq, const float bmin[3], const float bmax[3],
                             SortScratch &s, uint32_t **perm_out, int64_t *nvalid, hipStream_t st,
-                            bool surf) {
+                            bool surf, const uint32_t *app_order) {
   *perm_out = nullptr;
   *nvalid = 0;
   if (nq <= 0) return hipSuccess;
@@ -543,7 +554,7 @@ hipError_t curve_order_rows(const float4 *q, int64_t nprim, const uint64_t *qmas
                                                              (uint32_t *)s.k0.p, (uint32_t *)s.v0.p);
   if (napp > 0)
     append_keys_kernel<<<(unsigned)((napp + 255) / 256), 256, 0, st>>>(
-        q, qbase, napp, (int64_t)ndet, g, (uint32_t *)s.k0.p, (uint32_t *)s.v0.p);
+        q, qbase, napp, (int64_t)ndet, g, (uint32_t *)s.k0.p, (uint32_t *)s.v0.p, app_order);
   // every compacted slot holds a query (the masks say so), so every key is below 2^30: 30 key
   // bits, and no count of the valid ones
   tb = 0;

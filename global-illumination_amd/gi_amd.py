@@ -16,6 +16,9 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
                    the accumulator (gi.h "variance-guided denoise")
   get_view / accum_reproject: the accumulator carried into a new camera (gi.h "reprojection
                    across views")
+  accum_export / accum_import / accum_merge / accum_export_packed / accum_merge_packed /
+  accum_merge_from: the accumulator's fp64 state out of its context, back in, and folded into
+                   another accumulator (gi.h "accumulator state")
   render_radiance / render_rays_radiance / accum_* / tonemap / write_image_float: unclamped
                    radiance frames with their variance, accumulation over passes and the tone
                    map (no reference counterpart; gi.h "radiance frames, accumulation over
@@ -54,6 +57,8 @@ EXPORTED = [
     "gi_accum_add_adaptive", "gi_adaptive_bench",
     "gi_vdenoise_params_default", "gi_denoise_radiance", "gi_accum_denoise",
     "gi_get_view", "gi_reproject_params_default", "gi_accum_reproject",
+    "gi_accum_export", "gi_accum_import", "gi_accum_merge", "gi_accum_export_packed",
+    "gi_accum_merge_packed", "gi_accum_merge_from",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
@@ -275,6 +280,13 @@ def lib():
         L.gi_reproject_params_default.restype = None
         L.gi_accum_reproject.argtypes = [C.c_void_p, P(View), C.c_void_p, C.c_void_p,
                                          P(ReprojectParams), P(ReprojectStats), P(C.c_double)]
+        L.gi_accum_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gi_accum_import.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gi_accum_merge.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gi_accum_export_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+        L.gi_accum_merge_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                            P(C.c_double)]
+        L.gi_accum_merge_from.argtypes = [C.c_void_p, C.c_void_p, P(C.c_double)]
         L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                  C.c_double, C.c_void_p, C.c_void_p]
         L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -646,6 +658,66 @@ class Renderer:
         self._check(lib().gi_accum_get_counts(self._ctx, counts.ctypes.data if w else None,
                                               C.byref(total)))
         return counts, total.value
+
+    def accum_export(self):
+        """(state [H, W, 6] float64: {mu.rgb, A.rgb}, counts [H, W] int64) of the accumulator, the
+        device's own bits (gi_accum_export)."""
+        w, h = getattr(self, "_accum_size", (0, 0))
+        state = np.zeros((h, w, 6), dtype=np.float64)
+        counts = np.zeros((h, w), dtype=np.int64)
+        self._check(lib().gi_accum_export(self._ctx, state.ctypes.data if w else None,
+                                          counts.ctypes.data if w else None))
+        return state, counts
+
+    @staticmethod
+    def _host_state(state, counts):
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if state.ndim != 3 or state.shape[2] != 6 or counts.shape != state.shape[:2]:
+            raise ValueError(f"state {state.shape} / counts {counts.shape} are not [H, W, 6] / [H, W]")
+        return state, counts
+
+    def accum_import(self, state, counts):
+        """Replace the accumulator by a state as accum_export returns it (gi_accum_import);
+        needs no scene and no reset."""
+        state, counts = self._host_state(state, counts)
+        h, w = counts.shape
+        self._check(lib().gi_accum_import(self._ctx, w, h, state.ctypes.data, counts.ctypes.data))
+        self._accum_size = (w, h)
+
+    def accum_merge(self, state, counts):
+        """Fold a state of the accumulator's size into it (gi_accum_merge)."""
+        state, counts = self._host_state(state, counts)
+        h, w = counts.shape
+        self._check(lib().gi_accum_merge(self._ctx, w, h, state.ctypes.data, counts.ctypes.data))
+
+    def accum_state_bytes(self):
+        """Bytes of the packed state (gi_accum_export_packed with a null buffer)."""
+        n = C.c_int64(0)
+        self._check(lib().gi_accum_export_packed(self._ctx, None, 0, C.byref(n)))
+        return n.value
+
+    def accum_export_packed(self, dev_ptr, capacity_bytes):
+        """The packed state into device memory at dev_ptr (on this renderer's device); returns its
+        bytes (gi_accum_export_packed)."""
+        n = C.c_int64(0)
+        self._check(lib().gi_accum_export_packed(self._ctx, dev_ptr, capacity_bytes, C.byref(n)))
+        return n.value
+
+    def accum_merge_packed(self, nstates, dev_ptr, stride_bytes):
+        """Fold nstates packed states at dev_ptr (device memory, stride_bytes apart) into the
+        accumulator in order, in one launch (gi_accum_merge_packed); returns its HIP-event ms."""
+        ms = C.c_double(0.0)
+        self._check(lib().gi_accum_merge_packed(self._ctx, nstates, dev_ptr, stride_bytes,
+                                                C.byref(ms)))
+        return ms.value
+
+    def accum_merge_from(self, other):
+        """Fold another renderer's accumulator (same size, on any device) into this one; the
+        other is left unchanged (gi_accum_merge_from). Returns the fold's HIP-event ms."""
+        ms = C.c_double(0.0)
+        self._check(lib().gi_accum_merge_from(self._ctx, other._ctx, C.byref(ms)))
+        return ms.value
 
     def _tiles(self, tile_px):
         w, h = getattr(self, "_accum_size", (0, 0))

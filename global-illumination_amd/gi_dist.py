@@ -18,6 +18,10 @@ Host path (gloo on CPU, and renderers without the packed entry point): gi_render
 f32 image holding this rank's tiles, its own pixels picked out on the host.
 
 (The single-process drop-in does the same over a device set in C++: gi_create_devices.)
+
+The progressive pipeline (accumulate_passes) is cut by passes instead of tiles: pass i goes to
+rank i % world, every rank accumulates its own passes, and rank 0 folds the ranks' accumulator
+states (56 B per pixel, one gather) in rank order.
 """
 import numpy as np
 
@@ -100,6 +104,57 @@ def render_sharded_packed(renderer, aa, width, height, tile, rank, world, dist, 
                                       want_float=True), st
     dist.gather(send, None, dst=0)
     return None, st
+
+
+def rank_passes(passes, rank, world):
+    """The passes of the progressive pipeline that a rank renders: i with i % world == rank."""
+    return list(range(rank, passes, world))
+
+
+def accumulate_passes(renderer, aa, width, height, passes, base_params, rank, world, dist, device):
+    """The progressive pipeline cut by passes (gi.h "accumulator state"): pass i is an
+    independent estimate from the same maps under seed base_params.seed + i, so rank r empties its
+    accumulator and adds the passes i % world == r; the ranks' packed states (56 B per pixel) are
+    gathered onto rank 0 in one gather and folded there, ranks 1 .. world - 1 in rank order, into
+    rank 0's accumulator by one gi_accum_merge_packed. The renderer holds the scene and the maps
+    built under the base seed (the same on every rank); its parameters are the base ones again
+    afterwards. Returns accum_get() of the merged accumulator on rank 0, None elsewhere.
+
+    The states travel device to device over RCCL; gloo goes through host copies, and a renderer
+    whose packed entry points read host memory (`packed_host_memory`) takes a CPU device, as in
+    render_sharded_packed."""
+    import torch
+    if device.type != "cuda" and not getattr(renderer, "packed_host_memory", False):
+        raise ValueError("accumulate_passes hands device pointers to the renderer: it needs a "
+                         "CUDA device")
+    seed = base_params.seed
+    renderer.accum_reset(width, height)
+    try:
+        for i in rank_passes(passes, rank, world):
+            base_params.seed = seed + i
+            renderer.set_params(base_params)
+            renderer.accum_add_image(aa)
+    finally:
+        base_params.seed = seed
+        renderer.set_params(base_params)
+    nbytes = width * height * 56
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)  # the library writes on its own stream
+    renderer.accum_export_packed(buf.data_ptr(), nbytes)
+    host = device.type == "cuda" and dist.get_backend() != "nccl"
+    send = buf.cpu() if host else buf
+    if rank != 0:
+        dist.gather(send, None, dst=0)
+        return None
+    allb = torch.empty((world, nbytes), dtype=torch.uint8, device=send.device)
+    dist.gather(send, list(allb.unbind(0)), dst=0)
+    if world > 1:
+        others = allb[1:].to(device) if host else allb[1:]
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        renderer.accum_merge_packed(world - 1, others.data_ptr(), nbytes)
+    return renderer.accum_get()
 
 
 def render_sharded(renderer, aa, width, height, tile, rank, world, dist, device=None):

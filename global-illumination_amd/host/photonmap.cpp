@@ -27,6 +27,16 @@
 // the accumulator is not emptied but carried into the new camera (gi_camera_features +
 // gi_accum_reproject with max_history = H); with -adaptive the view then goes straight to adaptive
 // passes, which refine the tiles whose history was lost.
+// Extension: -save_accum FILE, -load_accum FILE (radiance flags; not with -views): -save_accum
+// writes the accumulator's fp64 state as the pass loop leaves it (gi_accum_export; the file:
+// AccumFile below) with the number of pass-loop iterations behind it. -load_accum starts from
+// such a file instead of an empty accumulator (gi_accum_import): pass i runs under seed +
+// passes_done + i, -passes N means N more passes, and a saved file counts the loaded passes too,
+// so an interrupted run that is resumed ends with the bits of the uninterrupted one. A file that is
+// missing, short or long, of another magic or size than -resolution, or holds a negative count exits
+// -1. -noise T is tested after a pass, as without a file: a resumed run renders at least one pass,
+// also when the loaded state is already at T (the uninterrupted run would have stopped there, and
+// its file would not have been resumed).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -143,6 +153,7 @@ struct RadianceFlags {
   int passes = 0;  // 0: not given
   double noise = 0.0, exposure = 1.0, white = 0.0;
   const char *file = nullptr;
+  const char *save_accum = nullptr, *load_accum = nullptr;
 };
 // null, or the flag that is malformed
 static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
@@ -186,9 +197,73 @@ static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
     r.file = t;
     r.any = true;
   }
+  if (!TakeValue(argc, argv, "-save_accum", &r.save_accum)) return "-save_accum";
+  if (!TakeValue(argc, argv, "-load_accum", &r.load_accum)) return "-load_accum";
+  if (r.save_accum || r.load_accum) r.any = true;
   if (r.adaptive_tile && !r.have_noise) return "-adaptive";
   if (r.passes == 0) r.passes = r.have_noise ? 4096 : 1;
   return nullptr;
+}
+
+// The accumulator's file (gi.h "accumulator state", little-endian): a 32-byte header {"GIACC01\n",
+// int32 width, int32 height, int64 passes_done, 8 zero bytes}, the state plane (W*H*6 doubles),
+// the counts plane (W*H int64).
+static const char ACCUM_MAGIC[9] = "GIACC01\n";
+struct AccumFile {
+  std::vector<double> state;
+  std::vector<int64_t> counts;
+  int64_t passes_done = 0;
+};
+// empty, or why the file is not the state of a w x h accumulator
+static std::string ReadAccum(const char *path, int w, int h, AccumFile &a) {
+  FILE *f = fopen(path, "rb");
+  if (!f) return "cannot open it";
+  unsigned char head[32];
+  int32_t fw = 0, fh = 0;
+  std::string why;
+  if (fread(head, 1, 32, f) != 32) why = "shorter than its header";
+  else if (memcmp(head, ACCUM_MAGIC, 8)) why = "not an accumulator file (bad magic)";
+  else {
+    memcpy(&fw, head + 8, 4);
+    memcpy(&fh, head + 12, 4);
+    memcpy(&a.passes_done, head + 16, 8);
+    if (fw != w || fh != h)
+      why = "it holds " + std::to_string(fw) + " x " + std::to_string(fh) + " pixels, -resolution is " +
+            std::to_string(w) + " x " + std::to_string(h);
+    else if (a.passes_done < 0) why = "negative pass count";
+  }
+  if (why.empty()) {
+    const size_t npix = (size_t)w * h;
+    a.state.resize(npix * 6);
+    a.counts.resize(npix);
+    if (fread(a.state.data(), 8, npix * 6, f) != npix * 6 || fread(a.counts.data(), 8, npix, f) != npix)
+      why = "shorter than its " + std::to_string(32 + npix * 56) + " bytes";
+    else if (fgetc(f) != EOF)
+      why = "longer than its " + std::to_string(32 + npix * 56) + " bytes";
+    else
+      for (int64_t n : a.counts)
+        if (n < 0) {
+          why = "negative sample count";
+          break;
+        }
+  }
+  fclose(f);
+  return why;
+}
+static bool WriteAccum(const char *path, int w, int h, const AccumFile &a) {
+  FILE *f = fopen(path, "wb");
+  if (!f) return false;
+  unsigned char head[32];
+  const int32_t fw = w, fh = h;
+  memset(head, 0, sizeof head);
+  memcpy(head, ACCUM_MAGIC, 8);
+  memcpy(head + 8, &fw, 4);
+  memcpy(head + 12, &fh, 4);
+  memcpy(head + 16, &a.passes_done, 8);
+  bool ok = fwrite(head, 1, 32, f) == 32 &&
+            fwrite(a.state.data(), 8, a.state.size(), f) == a.state.size() &&
+            fwrite(a.counts.data(), 8, a.counts.size(), f) == a.counts.size();
+  return (fclose(f) == 0) && ok;
 }
 
 // -views FILE: one camera per line, ten numbers as in -camera; blank lines and lines starting with
@@ -282,6 +357,10 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (views_file && (rad.save_accum || rad.load_accum)) {
+    fprintf(stderr, "Invalid program argument: -views (not with -save_accum or -load_accum)\n");
+    return -1;
+  }
   if (views_file) {
     if (denoise_levels) {
       fprintf(stderr, "Invalid program argument: -views (not with -denoise)\n");
@@ -335,6 +414,14 @@ int main(int argc, char **argv) {
     fprintf(stderr, "-passes, -noise, -exposure, -white, -radiance, -vdenoise and -views render on one device: not with -gpus %d\n",
             ds.count);
     return -1;
+  }
+  AccumFile loaded;  // -load_accum: checked before a device is opened
+  if (rad.load_accum) {
+    const std::string why = ReadAccum(rad.load_accum, w, h, loaded);
+    if (!why.empty()) {
+      fprintf(stderr, "Unable to read -load_accum file %s: %s\n", rad.load_accum, why.c_str());
+      return -1;
+    }
   }
   gi_ctx *ctx = nullptr;
   if (gi_create_devices(&ctx, &ds) != GI_OK) {
@@ -429,14 +516,19 @@ int main(int argc, char **argv) {
           carried = ok;
         }
       }
-      if (ok && !carried) ok = gi_accum_reset(ctx, w, h) == GI_OK;
+      // -load_accum: the run continues the file's: its state, its seeds, and its smallest count, so
+      // that the adaptive branch decides as the uninterrupted run would
+      if (ok && rad.load_accum)
+        ok = gi_accum_import(ctx, w, h, loaded.state.data(), loaded.counts.data()) == GI_OK &&
+             gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
+      else if (ok && !carried) ok = gi_accum_reset(ctx, w, h) == GI_OK;
       gi_adaptive_params ap;
       gi_adaptive_params_default(&ap);
       ap.tile_px = rad.adaptive_tile ? rad.adaptive_tile : ap.tile_px;
       ap.threshold = rad.noise;
       for (int i = 0; ok && i < rad.passes; i++) {
         gi_params Pi = P;
-        Pi.seed = P.seed + (uint64_t)i;
+        Pi.seed = P.seed + (uint64_t)loaded.passes_done + (uint64_t)i;
         gi_render_stats ps;
         prog.last[0] = -1;
         ok = gi_set_params(ctx, &Pi) == GI_OK;
@@ -472,6 +564,18 @@ int main(int argc, char **argv) {
         ok = gi_accum_get_counts(ctx, counts.data(), &total) == GI_OK;
         acc_total = total;
         for (int64_t v : counts) acc_max = v > acc_max ? v : acc_max;
+      }
+      if (ok && rad.save_accum) {  // the accumulator as the pass loop leaves it
+        AccumFile out_acc;
+        out_acc.state.resize((size_t)w * h * 6);
+        out_acc.counts.resize((size_t)w * h);
+        out_acc.passes_done = loaded.passes_done + passes_done;
+        ok = gi_accum_export(ctx, out_acc.state.data(), out_acc.counts.data()) == GI_OK;
+        if (ok && !WriteAccum(rad.save_accum, w, h, out_acc)) {
+          fprintf(stderr, "Unable to write -save_accum file %s\n", rad.save_accum);
+          gi_destroy(ctx);
+          return -1;
+        }
       }
       int64_t n = 0;
       ok = ok && gi_accum_get(ctx, mean.data(), nullptr, &n, &acc_noise) == GI_OK;

@@ -383,6 +383,62 @@ int gi_accum_get(gi_ctx *ctx, float *mean, float *variance, int64_t *nsamples, d
 /* counts: W*H int64, rows from the bottom (optional); *total = sum of n_p (optional) */
 int gi_accum_get_counts(gi_ctx *ctx, int64_t *counts, int64_t *total);
 
+/* ---- accumulator state: export, import and merge ------------------------------------------ */
+/* The state of a W x H accumulator (DESIGN.md "Accumulator state"), the device's own bits with no
+ * rounding:
+ *   state   W*H*6 doubles, pixel-major, rows from the bottom: {mu_r, mu_g, mu_b, A_r, A_g, A_b}
+ *   counts  W*H int64 n_p
+ * Packed state: one buffer of W*H*56 bytes, the state plane (48 W H bytes) and then the counts
+ * plane (8 W H bytes).
+ * The fold of state b into state a, per pixel and channel in fp64, each step one IEEE operation
+ * in the order written:
+ *   n_b == 0:  a unchanged (bit for bit)
+ *   n_a == 0:  a = b (bit copy of mu and A; n = n_b)
+ *   else:      Na = (double)n_a, Nb = (double)n_b, N1 = (double)(n_a + n_b), NS = Na * Nb
+ *              d = mu_b - mu_a
+ *              mu' = mu_a + (d * Nb) / N1
+ *              A'  = (A_a + A_b) + ((d * d) * NS) / N1
+ *              n'  = n_a + n_b
+ * This is the pass update above with S = n_b, m = mu_b, M2 = A_b, so folding the state of a
+ * context that holds one pass equals adding that pass. K states are folded as ((a + b_0) + b_1)
+ * + ... in the given order; the fold is not associative in bits, so the order is part of the
+ * result. All six calls: GI_ERR_UNSUPPORTED on a device set, GI_ERR_STATE where they need an
+ * accumulator (all but gi_accum_import) and there is none. After an import or a merge every pixel
+ * is under its own count, as after gi_accum_reproject, and every other accumulator call behaves
+ * as on any accumulator with those bits. No reference counterpart.
+ *
+ * gi_accum_export: the state to host buffers; either may be NULL, not both.
+ * gi_accum_import: sizes the accumulator like gi_accum_reset(width, height) and replaces it by
+ * the host state; needs only a context (no scene, no earlier reset). A negative count is
+ * GI_ERR_ARG and leaves the accumulator as it was. mu and A are not scanned: a NaN or Inf in them
+ * is taken as it is.
+ * gi_accum_merge: folds one host state into the accumulator. GI_ERR_ARG (accumulator unchanged)
+ * for a width x height other than the accumulator's or a negative count. */
+int gi_accum_export(gi_ctx *ctx, double *state, int64_t *counts);
+int gi_accum_import(gi_ctx *ctx, int width, int height, const double *state, const int64_t *counts);
+int gi_accum_merge(gi_ctx *ctx, int width, int height, const double *state, const int64_t *counts);
+/* The packed state written to `packed`, a DEVICE pointer on the context's device holding
+ * capacity_bytes; *bytes (optional with a buffer) = W*H*56, and packed == NULL only reports it. A
+ * capacity below that is GI_ERR_ARG. Synchronous; restores the calling thread's current HIP
+ * device, like the other packed entry points. */
+int gi_accum_export_packed(gi_ctx *ctx, void *packed /* DEVICE */, int64_t capacity_bytes,
+                           int64_t *bytes);
+/* nstates >= 1 packed states, state s at packed + s * stride_bytes in DEVICE memory of the
+ * context's device (the layout of a gather of gi_accum_export_packed outputs), folded into the
+ * accumulator in the order s = 0 .. nstates - 1 by one launch that reads the accumulator once,
+ * each state once, and writes each pixel once. stride_bytes >= W*H*56; packed and stride_bytes
+ * are multiples of 8, so that every plane is aligned for its doubles and int64 (else GI_ERR_ARG):
+ * padding after a state is allowed. The caller guarantees nstates * stride_bytes
+ * bytes. The device counts are not scanned: a negative one is folded as it is. kernel_ms
+ * (optional): HIP-event time of the launch. Synchronous; restores the current HIP device. */
+int gi_accum_merge_packed(gi_ctx *ctx, int nstates, const void *packed /* DEVICE */,
+                          int64_t stride_bytes, double *kernel_ms /* optional */);
+/* The accumulator of src folded into dst's: two one-device contexts (on one device or on two)
+ * whose accumulators have the same size (else GI_ERR_ARG; dst == src is GI_ERR_ARG). The source's
+ * state is copied to the destination's device and folded there; src is left bit for bit
+ * unchanged. */
+int gi_accum_merge_from(gi_ctx *dst, gi_ctx *src, double *kernel_ms /* optional */);
+
 /* ---- adaptive passes: refine only the noisy tiles of the accumulator --------------------- */
 /* The accumulator's frame is cut into tiles of tile_px x tile_px pixels: tiles_x = ceil(W /
  * tile_px), tiles_y likewise, tile t = ty * tiles_x + tx with ty = 0 at the bottom; the tiles of
