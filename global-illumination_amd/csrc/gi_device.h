@@ -452,6 +452,8 @@ constexpr uint32_t KIND_BIT(int k) { return 1u << k; }
 constexpr uint32_t KINDS_ALL = ~0u;
 constexpr uint32_t KINDS_TRI_SPHERE = (1u << SK_TRI) | (1u << SK_SPHERE);
 constexpr uint32_t KINDS_POLY = (1u << SK_TRI) | (1u << SK_SPHERE) | (1u << SK_MESH) | (1u << SK_BOX);
+// a scene's kinds (SceneView::kinds) hold nothing outside set: the instance for set covers it
+constexpr bool kinds_within(uint32_t kinds, uint32_t set) { return (kinds & ~set) == 0; }
 
 // R3Shape::Intersects dispatch (R3Shape.cpp:328-329); SK_MESH is R3Intersects(ray,
 // R3TriangleArray) (R3Isect.cpp:800-833): min t over ALL triangles, t >= -1e-6 allowed (Q2).

@@ -578,7 +578,7 @@ static int path_setup(gi_ctx *c, RenderArgs &a, Batch &B) {
     // on, hard lights over triangles and spheres only (C2 -2.0 %; 4 and 8 rounds measured the
     // same, 16 no better). Soft-light scenes keep the persistent kernel, the other hard-light
     // element sets (whose step kernels spill) mc_kernel.
-    const bool wave_class = a.S.hard_lights && (a.S.kinds & ~KINDS_TRI_SPHERE) == 0;
+    const bool wave_class = a.S.hard_lights && kinds_within(a.S.kinds, KINDS_TRI_SPHERE);
     const int rounds = c->mc_persist > 0 ? 0 : c->mc_wave >= 0 ? c->mc_wave : wave_class ? 4 : 0;
     if (rounds > 0) {
       HIPCHK(c, c->s.mc_wstate.ensure((size_t)a.total_mc * sizeof(McState)));

@@ -12,6 +12,7 @@
 // The decomposition is exact: every k-NN estimate enters the pixel linearly (colour += w*est),
 // so deferring the estimates into a query list changes only the fp summation order.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gi_device.h"
 #include "gi_kernels.h"
 #include "gi_estimate.h"
@@ -285,6 +286,20 @@ __device__ __forceinline__ void put_none(const RenderArgs &a, int list, int64_t 
   if (keyed_slot(a, list, slot)) a.qkey[list][slot] = ~0ull;
 }
 
+// Wave-aggregated slot claim: the lanes that call this (any subset of the wave, the lanes active
+// at the call) each get a distinct index from *counter, through one atomic by the first of them
+// (a single counter word serialises ~10^8 atomics/s, MI355X_MICROARCH.md 'dequeue'). Every
+// queue, list and photon append of this file takes its slot here.
+__device__ __forceinline__ uint32_t wave_take(uint32_t *counter) {
+  const uint64_t act = __ballot(1);
+  const int lane = (int)(threadIdx.x & 63);
+  const int leader = __ffsll((long long)act) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(act));
+  base = (uint32_t)__shfl((int)base, leader, 64);
+  return base + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+}
+
 // append one photon-map query (list 0 = global, 1 = caustic): search half (point as f32 +
 // meta) and shading half (normal, exact bounce, path weight)
 __device__ __forceinline__ void put_query(PathCtx &P, int list, V p, V n, V ex, double ct,
@@ -295,16 +310,7 @@ __device__ __forceinline__ void put_query(PathCtx &P, int list, V p, V n, V ex, 
     slot = (uint32_t)P.fixed[list];
     P.fixed[list] = -2;
   } else {
-    // one atomic per wave for all lanes that emit here (a single counter word serialises
-    // ~10^8 atomics/s, MI355X_MICROARCH.md 'dequeue')
-    uint64_t act = __ballot(1);
-    int lane = (int)(threadIdx.x & 63);
-    int leader = __ffsll((long long)act) - 1;
-    uint32_t rank = (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&a.qcount[list], (uint32_t)__popcll(act));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    slot = base + rank;
+    slot = wave_take(&a.qcount[list]);  // one atomic per wave for all lanes that emit here
   }
   // order key: (primary, slot in primary, query in path) -- the per-pixel reduction sums each
   // primary's queries in this order; segments per primary come from one boundary pass
@@ -411,24 +417,11 @@ __device__ __noinline__ void mc_indirect(PathCtx &P, V org, V dir, Rng &rng, C3 
   mc_indirect_body<KINDS>(P, org, dir, rng, W);
 }
 
-// List compaction for the breadth-first path schedules. Both take one atomic per wave (per
-// stripe), like put_query; the order of the entries within a list is free.
-//
-// Every lane of the wave calls this; the lanes with keep set append v to list (their count
-// added to *count by the first of them).
-__device__ __forceinline__ void wave_list_append(uint32_t *list, uint32_t *count, bool keep,
-                                                 uint32_t v) {
-  const uint64_t m = __ballot(keep);
-  if (m == 0) return;
-  const int lane = (int)(threadIdx.x & 63);
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t b = 0;
-  if (lane == leader) b = atomicAdd(count, (uint32_t)__popcll(m));
-  b = (uint32_t)__shfl((int)b, leader, 64);
-  if (keep) list[b + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
-}
 // The calling lanes (any subset of the wave) each take an entry of the striped queue whose
-// fill counters are fill[stripe * 32]: returns the lane's index within its stripe.
+// fill counters are fill[stripe * 32]: returns the lane's index within its stripe. wave_take's
+// step once per stripe present among the callers, on the group's mask instead of the active
+// lanes' (written out: with wave_take under `if (stripe == ls)` the tail instance of
+// mc_wave_step_kernel for triangles and spheres spills 2 VGPRs, written out none).
 __device__ __forceinline__ uint32_t wave_stripe_append(uint32_t *fill, uint32_t stripe) {
   const int lane = (int)(threadIdx.x & 63);
   uint64_t rem = __ballot(1);
@@ -444,6 +437,49 @@ __device__ __forceinline__ uint32_t wave_stripe_append(uint32_t *fill, uint32_t 
     rem &= ~grp;
   }
   return idx;
+}
+
+// The writers of a continuation queue entry (gi_kernels.h IndCont).
+// An entry queued at the hit h of the ray from org. SUB: a Monte Carlo path's sub-path, which
+// carries its path's query count j; an indirect sample path starts at 0 and stores none.
+template <bool SUB>
+__device__ __forceinline__ void ind_cont_at_hit(IndCont &q, V org, const Hit &h, C3 w,
+                                                const Rng &rng, uint32_t g, uint32_t prim,
+                                                uint32_t pslot, uint32_t qslot, uint32_t j = 0) {
+  q.org[0] = org.x; q.org[1] = org.y; q.org[2] = org.z;
+  q.hp[0] = h.p.x; q.hp[1] = h.p.y; q.hp[2] = h.p.z;
+  q.hn[0] = h.n.x; q.hn[1] = h.n.y; q.hn[2] = h.n.z;
+  q.w[0] = w.r; q.w[1] = w.g; q.w[2] = w.b;
+  q.rkey = rng.key;
+  q.rctr = rng.ctr;
+  q.g = g;
+  q.prim = prim;
+  q.pslot = pslot;
+  q.qslot = qslot;
+  q.mat = h.mat;
+  if (SUB) q.j = j;
+  q.tri = h.tri;
+  q.sub = SUB ? 1 : 0;
+}
+// The sub-path of Monte Carlo path P queued as a ray (org, dir) leaving triangle tri: no hit
+// yet, mat = -1. The path's fields are read from P where they are stored: with them passed by
+// value (the slot's select evaluated before the stores) the soft-light instances of
+// mc_persist_kernel spilled 2 VGPRs more.
+__device__ __forceinline__ void ind_cont_ray(IndCont &q, V org, V dir, C3 w, const Rng &rng,
+                                             const PathCtx &P, int tri) {
+  q.org[0] = org.x; q.org[1] = org.y; q.org[2] = org.z;
+  q.hp[0] = dir.x; q.hp[1] = dir.y; q.hp[2] = dir.z;
+  q.w[0] = w.r; q.w[1] = w.g; q.w[2] = w.b;
+  q.rkey = rng.key;
+  q.rctr = rng.ctr;
+  q.g = (uint32_t)P.g;
+  q.prim = P.prim;
+  q.pslot = P.pslot;
+  q.qslot = P.fixed[0] >= 0 ? (uint32_t)P.fixed[0] : 0xffffffffu;
+  q.mat = -1;
+  q.j = P.j;
+  q.tri = tri;
+  q.sub = 0;
 }
 
 // MonteCarlo_PathTrace's loop state (montecarlo.cpp:16-171): the current ray, the loop's
@@ -528,28 +564,9 @@ __device__ __forceinline__ bool mc_step(PathCtx &P, McLoop &L) {
           e = (size_t)P.qstripe * P.A->mc_cap_s +
               wave_stripe_append(P.A->mc_ncont, P.qstripe);
         } else {  // mc_kernel: one atomic per wave on its stripe
-          int lane = (int)(threadIdx.x & 63);
-          uint64_t act = __ballot(1);
-          int leader = __ffsll((long long)act) - 1;
-          uint32_t qb = 0;
-          if (lane == leader) qb = atomicAdd(&P.A->mc_ncont[P.qstripe * 32], (uint32_t)__popcll(act));
-          qb = (uint32_t)__shfl((int)qb, leader, 64);
-          e = (size_t)P.qstripe * P.A->mc_cap_s + qb + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+          e = (size_t)P.qstripe * P.A->mc_cap_s + wave_take(&P.A->mc_ncont[P.qstripe * 32]);
         }
-        IndCont &q = P.A->mc_cont[e];
-        q.org[0] = o2.x; q.org[1] = o2.y; q.org[2] = o2.z;
-        q.hp[0] = s2.x; q.hp[1] = s2.y; q.hp[2] = s2.z;
-        q.w[0] = w2.r; q.w[1] = w2.g; q.w[2] = w2.b;
-        q.rkey = rng.key;
-        q.rctr = rng.ctr;
-        q.g = (uint32_t)P.g;
-        q.prim = P.prim;
-        q.pslot = P.pslot;
-        q.qslot = P.fixed[0] >= 0 ? (uint32_t)P.fixed[0] : 0xffffffffu;
-        q.mat = -1;
-        q.j = P.j;
-        q.tri = h.tri;
-        q.sub = 0;
+        ind_cont_ray(P.A->mc_cont[e], o2, s2, w2, rng, P, h.tri);
         P.fixed[0] = -2;  // the sub-path owns the global slot now
       } else {
         mc_indirect<KINDS>(P, h.p + s2 * kEps, s2, rng, w2);
@@ -580,17 +597,6 @@ __device__ __forceinline__ bool mc_step(PathCtx &P, McLoop &L) {
   L.org = L.ray_start;
   L.dir = sb;
   return true;
-}
-
-// MonteCarlo_PathTrace, montecarlo.cpp:16-171
-template <uint32_t KINDS = KINDS_ALL, bool DEFER = false, bool HARD = false>
-__device__ __forceinline__ void mc_path(PathCtx &P, V org, V dir, Rng &rng, C3 W) {
-  if (!P.F->monte_carlo) return;
-  McLoop L;
-  mc_begin(L, org, dir, rng, W);
-  while (mc_step<KINDS, DEFER, HARD>(P, L)) {
-  }
-  rng = L.rng;
 }
 
 // last p in [0, n) with off[p] <= t (off is an exclusive scan, off[0] = 0)
@@ -631,6 +637,23 @@ __global__ void owner_table_kernel(const uint32_t *off, int64_t n, uint32_t *tab
 __device__ __forceinline__ bool base_is_pzero(const C3 &c) {
   return __double_as_longlong(c.r) == 0 && __double_as_longlong(c.g) == 0 &&
          __double_as_longlong(c.b) == 0;
+}
+// path slot g's base colour: written by the path that owns the slot, added to by its deferred
+// sub-path (the last term of the path's sum)
+__device__ __forceinline__ void store_base(const RenderArgs &a, int64_t g, const C3 &c) {
+  a.base[3 * g] = c.r;
+  a.base[3 * g + 1] = c.g;
+  a.base[3 * g + 2] = c.b;
+}
+__device__ __forceinline__ void add_base(const RenderArgs &a, int64_t g, const C3 &c) {
+  double *bp = a.base + 3 * g;
+  bp[0] = bp[0] + c.r;
+  bp[1] = bp[1] + c.g;
+  bp[2] = bp[2] + c.b;
+}
+__device__ __forceinline__ void counts_add(Counts &c, const Counts &d) {
+  c.shadow += d.shadow; c.monte += d.monte; c.trans += d.trans;
+  c.spec += d.spec; c.indirect += d.indirect; c.caustic += d.caustic;
 }
 
 // tiled entry of indirect path s of primary b (RenderArgs::ind_rows)
@@ -740,9 +763,7 @@ __global__ __launch_bounds__(256) void slot0_kernel(RenderArgs a) {
     }
     if (P.fixed[0] >= 0) put_none(a, 0, b);
     if (P.fixed[1] >= 0) put_none(a, 1, b);
-    a.base[3 * g] = P.base.r;
-    a.base[3 * g + 1] = P.base.g;
-    a.base[3 * g + 2] = P.base.b;
+    store_base(a, g, P.base);
     cnt = P.cnt;
   }
   path_stats(a, cnt);
@@ -809,31 +830,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
         } else {
           // glass / mirror hit: shaded in ind_cont_kernel (wave-aggregated append)
           queue = true;
-          uint64_t act = __ballot(1);
-          int lane = (int)(threadIdx.x & 63);
-          int leader = __ffsll((long long)act) - 1;
           const uint32_t stripe = (uint32_t)(t >> 6) & (IND_QS - 1);
-          uint32_t base = 0;
-          if (lane == leader) base = atomicAdd(&a.ind_ncont[stripe * 32], (uint32_t)__popcll(act));
-          base = (uint32_t)__shfl((int)base, leader, 64);
-          const uint32_t slot = base + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+          const uint32_t slot = wave_take(&a.ind_ncont[stripe * 32]);
           // a full stripe drops the entry; the host sees the fill and re-runs the batch
-          IndCont &q = a.ind_cont[(size_t)stripe * a.ind_cap_s + (slot < a.ind_cap_s ? slot : 0)];
-          if (slot < a.ind_cap_s) {
-          q.org[0] = org.x; q.org[1] = org.y; q.org[2] = org.z;
-          q.hp[0] = h.p.x; q.hp[1] = h.p.y; q.hp[2] = h.p.z;
-          q.hn[0] = h.n.x; q.hn[1] = h.n.y; q.hn[2] = h.n.z;
-          q.w[0] = Wt.r; q.w[1] = Wt.g; q.w[2] = Wt.b;
-          q.rkey = rng.key;
-          q.rctr = rng.ctr;
-          q.g = (uint32_t)g;
-          q.prim = (uint32_t)pb;
-          q.pslot = (uint32_t)pslot;
-          q.qslot = (uint32_t)P.fixed[0];
-          q.mat = h.mat;
-          q.tri = h.tri;
-          q.sub = 0;
-          }
+          if (slot < a.ind_cap_s)
+            ind_cont_at_hit<false>(a.ind_cont[(size_t)stripe * a.ind_cap_s + slot], org, h, Wt, rng,
+                                   (uint32_t)g, (uint32_t)pb, (uint32_t)pslot,
+                                   (uint32_t)P.fixed[0]);
         }
       }
     }
@@ -842,11 +845,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
       hasq = P.fixed[0] == -2;
       if (P.fixed[0] >= 0) put_none(a, 0, P.fixed[0]);
       hasb = !base_is_pzero(P.base);
-      if (hasb) {
-        a.base[3 * g] = P.base.r;
-        a.base[3 * g + 1] = P.base.g;
-        a.base[3 * g + 2] = P.base.b;
-      }
+      if (hasb) store_base(a, g, P.base);
     }
     cnt = P.cnt;
   }
@@ -881,6 +880,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W))) void i
 // first hit, then MonteCarlo_IndirectSample's loop from iteration 1 on; ray entries
 // (mat == -1): the whole loop, its contribution added to the Monte Carlo path's base.
 // occupancy: 3 waves per SIMD; scenes with meshes / boxes (C4: 148 VGPRs spilled at 3) get 2
+// The walk over the stripe is written out here and in mc_sub_kernel: as a shared function taking
+// the body as a callable, or yielding the entry index, the triangle-and-sphere instance of this
+// kernel spilled 7 VGPRs instead of 6 in every form tried.
 template <uint32_t KINDS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu((KINDS & ~KINDS_TRI_SPHERE) ? 2 : 3)))
 void ind_cont_kernel(RenderArgs a, const IndCont *queue, const uint32_t *fill, uint32_t cap_s) {
@@ -927,30 +929,24 @@ void ind_cont_kernel(RenderArgs a, const IndCont *queue, const uint32_t *fill, u
         if (!ind_bounce<KINDS>(P, org, dir, rng, W, tw)) break;
     const bool used = P.fixed[0] == -2;
     if (P.fixed[0] >= 0) put_none(a, 0, P.fixed[0]);
-    double *bp = a.base + 3 * (int64_t)q.g;
     if (q.mat >= 0 && !sub) {
       // an indirect path's tiled entry (q.qslot = qind_base + tau): its mask bits
       const int64_t tau = (int64_t)q.qslot - a.qind_base;
       const unsigned long long bit = 1ull << (tau & 63);
       if (used) atomicOr((unsigned long long *)&a.ind_qmask[tau >> 6], bit);
       if (!base_is_pzero(P.base)) {
-        bp[0] = P.base.r;
-        bp[1] = P.base.g;
-        bp[2] = P.base.b;
+        store_base(a, q.g, P.base);
         atomicOr((unsigned long long *)&a.ind_bmask[tau >> 6], bit);
       }
     } else {  // the sub-path's background term is the last addition to the path's sum
-      bp[0] = bp[0] + P.base.r;
-      bp[1] = bp[1] + P.base.g;
-      bp[2] = bp[2] + P.base.b;
+      add_base(a, q.g, P.base);
     }
-    tot.shadow += P.cnt.shadow; tot.monte += P.cnt.monte; tot.trans += P.cnt.trans;
-    tot.spec += P.cnt.spec; tot.indirect += P.cnt.indirect; tot.caustic += P.cnt.caustic;
+    counts_add(tot, P.cnt);
   }
   path_stats(a, tot);
 }
 
-// The Monte Carlo paths' indirect sub-paths (mc_path's deferred IndirectIllumination sample,
+// The Monte Carlo paths' indirect sub-paths (mc_step's deferred IndirectIllumination sample,
 // montecarlo.cpp:177-305 from a diffuse hit): their first bounce, one per thread, in the lean
 // shape of ind_kernel. A sub-path that hits a diffuse-only material ends there (its query, or
 // its background term), as most do; one that hits glass or a mirror is queued at that hit to
@@ -1006,44 +1002,16 @@ void mc_sub_kernel(RenderArgs a, const IndCont *queue, const uint32_t *fill, uin
     }
     // glass / mirror first hits: wave-aggregated append to the same stripe of mc_cont2 (at most
     // this stripe's fill, so within its capacity)
-    const uint64_t act = __ballot(queue_it);
-    if (act) {
-      const int lane = (int)(threadIdx.x & 63);
-      const int leader = __ffsll((long long)act) - 1;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&a.mc_ncont2[stripe * 32], (uint32_t)__popcll(act));
-      base = (uint32_t)__shfl((int)base, leader, 64);
-      if (queue_it) {
-        IndCont &o = a.mc_cont2[(size_t)stripe * cap_s + base +
-                                (uint32_t)__popcll(act & ((1ull << lane) - 1ull))];
-        o.org[0] = org.x; o.org[1] = org.y; o.org[2] = org.z;
-        o.hp[0] = h.p.x; o.hp[1] = h.p.y; o.hp[2] = h.p.z;
-        o.hn[0] = h.n.x; o.hn[1] = h.n.y; o.hn[2] = h.n.z;
-        o.w[0] = W.r; o.w[1] = W.g; o.w[2] = W.b;
-        o.rkey = rng.key;
-        o.rctr = rng.ctr;
-        o.g = q.g;
-        o.prim = q.prim;
-        o.pslot = q.pslot;
-        o.qslot = q.qslot;
-        o.mat = h.mat;
-        o.j = P.j;
-        o.tri = h.tri;
-        o.sub = 1;
-      }
-    }
+    if (queue_it)
+      ind_cont_at_hit<true>(
+          a.mc_cont2[(size_t)stripe * cap_s + wave_take(&a.mc_ncont2[stripe * 32])], org, h, W,
+          rng, q.g, q.prim, q.pslot, q.qslot, P.j);
     if (on && !queue_it) {
       if (P.fixed[0] >= 0) put_none(a, 0, P.fixed[0]);
       // the sub-path's background term is the last addition to the path's sum
-      double *bp = a.base + 3 * (int64_t)q.g;
-      bp[0] = bp[0] + P.base.r;
-      bp[1] = bp[1] + P.base.g;
-      bp[2] = bp[2] + P.base.b;
+      add_base(a, q.g, P.base);
     }
-    if (on) {
-      tot.shadow += P.cnt.shadow; tot.monte += P.cnt.monte; tot.trans += P.cnt.trans;
-      tot.spec += P.cnt.spec; tot.indirect += P.cnt.indirect; tot.caustic += P.cnt.caustic;
-    }
+    if (on) counts_add(tot, P.cnt);
   }
   path_stats(a, tot);
 }
@@ -1051,47 +1019,64 @@ void mc_sub_kernel(RenderArgs a, const IndCont *queue, const uint32_t *fill, uin
 #ifndef MC_WPE
 #define MC_WPE 2  // mc_kernel occupancy target (waves per SIMD; 3 measured slower: spills)
 #endif
-// TransmissiveIllumination / SpecularIllumination sample (raytracer.cpp:47-109)
+// The start of Monte Carlo path t of the batch, shared by the three schedules below: its
+// primary sample (owner of t in mc_off), the TransmissiveIllumination / SpecularIllumination
+// sample that spawns it (raytracer.cpp:47-109: the sample's own RNG stream, the bounce off the
+// primary hit, the weight over n_t or n_s, its counter) and MonteCarlo_PathTrace's loop state
+// at its first ray. P.qstripe is the stripe of the calling wave. cont_slot: the path's fixed
+// mc_cont entry (PathCtx::cont_slot; the persistent kernel's t). It is set here, where that
+// kernel set it: set after the call, its soft-light instances spilled 2 VGPRs more.
+template <bool RAYS>
+__device__ __forceinline__ void mc_prologue(const RenderArgs &a, int64_t t, PathCtx &P, McLoop &L,
+                                            int64_t cont_slot = -1) {
+  const SceneView &S = a.S;
+  const Flags &F = a.F;
+  int64_t pb = wave_owner(a.mc_off, a.nprim, t, a.total_mc, a.mc_tab);
+  int s = (int)(t - a.mc_off[pb]);
+  const Spawn &sp = a.spawn[pb];
+  int64_t g = (int64_t)a.path_off[pb] + 1 + s;
+  int pix, i, j, k;
+  uint64_t psample;
+  decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
+  const DMaterial &m = S.mats[sp.mat];
+  V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
+  double ct = sp.ct, R = sp.R;
+  path_init(P, a, g, pb, 1 + s);
+  P.hint = sp.tri;
+  P.cont_slot = cont_slot;
+  Rng rng;
+  V sb;
+  C3 w;
+  if (s < sp.n_t) {
+    rng.init(F.seed, KIND_TRANS, psample, (uint64_t)s);
+    V ex = transmissive_bounce_nc(F.ir_air, n, view, ct, m.ir);
+    sb = F.distrib_trans ? specular_sample_call(ex, m.n, ct, rng) : ex;
+    w = ((1.0 - R) * ldc(m.kt)) / (double)sp.n_t;
+    P.cnt.trans++;
+  } else {
+    s -= sp.n_t;
+    rng.init(F.seed, KIND_SPEC, psample, (uint64_t)s);
+    V ex = reflective_bounce(n, view, ct);
+    sb = F.distrib_spec ? specular_sample_call(ex, m.n, ct, rng) : ex;
+    w = (ldc(m.kt) * R + ldc(m.ks)) / (double)sp.n_s;
+    P.cnt.spec++;
+  }
+  mc_begin(L, p + sb * kEps, sb, rng, w);
+  if (!F.monte_carlo) L.iter = F.max_monte_depth;  // MonteCarlo_PathTrace returns at once
+}
+
+// One path per lane, run to its end (MonteCarlo_PathTrace, montecarlo.cpp:16-171)
 template <uint32_t KINDS, bool DEFER, bool HARD, bool RAYS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE))) void mc_kernel(RenderArgs a) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   Counts cnt = {0, 0, 0, 0, 0, 0};
   if (t < a.total_mc) {
-    int64_t pb = wave_owner(a.mc_off, a.nprim, t, a.total_mc, a.mc_tab);
-    int s = (int)(t - a.mc_off[pb]);
-    const Spawn &sp = a.spawn[pb];
-    int64_t g = (int64_t)a.path_off[pb] + 1 + s;
-    int pix, i, j, k;
-    uint64_t psample;
-    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
-    const SceneView &S = a.S;
-    const Flags &F = a.F;
-    const DMaterial &m = S.mats[sp.mat];
-    V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
-    double ct = sp.ct, R = sp.R;
     PathCtx P;
-    path_init(P, a, g, pb, 1 + s);
-    P.hint = sp.tri;
-    Rng rng;
-    if (s < sp.n_t) {
-      rng.init(F.seed, KIND_TRANS, psample, (uint64_t)s);
-      V ex = transmissive_bounce_nc(F.ir_air, n, view, ct, m.ir);
-      C3 tw = (1.0 - R) * ldc(m.kt);
-      V sb = F.distrib_trans ? specular_sample_call(ex, m.n, ct, rng) : ex;
-      mc_path<KINDS, DEFER, HARD>(P, p + sb * kEps, sb, rng, tw / (double)sp.n_t);
-      P.cnt.trans++;
-    } else {
-      s -= sp.n_t;
-      rng.init(F.seed, KIND_SPEC, psample, (uint64_t)s);
-      V ex = reflective_bounce(n, view, ct);
-      C3 tw = ldc(m.kt) * R + ldc(m.ks);
-      V sb = F.distrib_spec ? specular_sample_call(ex, m.n, ct, rng) : ex;
-      mc_path<KINDS, DEFER, HARD>(P, p + sb * kEps, sb, rng, tw / (double)sp.n_s);
-      P.cnt.spec++;
+    McLoop L;
+    mc_prologue<RAYS>(a, t, P, L);
+    while (mc_step<KINDS, DEFER, HARD>(P, L)) {
     }
-    a.base[3 * g] = P.base.r;
-    a.base[3 * g + 1] = P.base.g;
-    a.base[3 * g + 2] = P.base.b;
+    store_base(a, P.g, P.base);
     cnt = P.cnt;
   }
   path_stats(a, cnt);
@@ -1106,9 +1091,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
 template <uint32_t KINDS, bool DEFER, bool HARD, bool RAYS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MC_WPE)))
 void mc_persist_kernel(RenderArgs a) {
-  const int lane = (int)(threadIdx.x & 63);
-  const SceneView &S = a.S;
-  const Flags &F = a.F;
   Counts cnt = {0, 0, 0, 0, 0, 0};
   PathCtx P;
   McLoop L;
@@ -1121,46 +1103,9 @@ void mc_persist_kernel(RenderArgs a) {
   }
   while (true) {
     if (!active && more) {
-      uint64_t need = __ballot(1);
-      int leader = __ffsll((long long)need) - 1;
-      uint32_t b = 0;
-      if (lane == leader) b = atomicAdd(a.mc_next, (uint32_t)__popcll(need));
-      b = (uint32_t)__shfl((int)b, leader, 64);
-      int64_t t = (int64_t)b + __popcll(need & ((1ull << lane) - 1ull));
+      const int64_t t = wave_take(a.mc_next);
       if (t < a.total_mc) {
-        // mc_kernel's prologue: the path's primary, its first (transmissive / specular) sample
-        int64_t pb = wave_owner(a.mc_off, a.nprim, t, a.total_mc, a.mc_tab);
-        int s = (int)(t - a.mc_off[pb]);
-        const Spawn &sp = a.spawn[pb];
-        int64_t g = (int64_t)a.path_off[pb] + 1 + s;
-        int pix, i, j, k;
-        uint64_t psample;
-        decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
-        const DMaterial &m = S.mats[sp.mat];
-        V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
-        double ct = sp.ct, R = sp.R;
-        path_init(P, a, g, pb, 1 + s);
-        P.hint = sp.tri;
-        P.cont_slot = t;
-        Rng rng;
-        V sb;
-        C3 w;
-        if (s < sp.n_t) {
-          rng.init(F.seed, KIND_TRANS, psample, (uint64_t)s);
-          V ex = transmissive_bounce_nc(F.ir_air, n, view, ct, m.ir);
-          sb = F.distrib_trans ? specular_sample_call(ex, m.n, ct, rng) : ex;
-          w = ((1.0 - R) * ldc(m.kt)) / (double)sp.n_t;
-          P.cnt.trans++;
-        } else {
-          s -= sp.n_t;
-          rng.init(F.seed, KIND_SPEC, psample, (uint64_t)s);
-          V ex = reflective_bounce(n, view, ct);
-          sb = F.distrib_spec ? specular_sample_call(ex, m.n, ct, rng) : ex;
-          w = (ldc(m.kt) * R + ldc(m.ks)) / (double)sp.n_s;
-          P.cnt.spec++;
-        }
-        mc_begin(L, p + sb * kEps, sb, rng, w);
-        if (!F.monte_carlo) L.iter = F.max_monte_depth;  // MonteCarlo_PathTrace returns at once
+        mc_prologue<RAYS>(a, t, P, L, t);
         active = true;
       } else {
         more = false;  // the counter only grows: this lane will find no more paths
@@ -1171,11 +1116,8 @@ void mc_persist_kernel(RenderArgs a) {
       // a path that deferred no sub-path marks its mc_cont entry empty (P.fixed[0] == -2 after
       // a deferral)
       if (DEFER && P.fixed[0] != -2) a.mc_cont[P.cont_slot].g = IND_EMPTY;
-      a.base[3 * P.g] = P.base.r;
-      a.base[3 * P.g + 1] = P.base.g;
-      a.base[3 * P.g + 2] = P.base.b;
-      cnt.shadow += P.cnt.shadow; cnt.monte += P.cnt.monte; cnt.trans += P.cnt.trans;
-      cnt.spec += P.cnt.spec; cnt.indirect += P.cnt.indirect; cnt.caustic += P.cnt.caustic;
+      store_base(a, P.g, P.base);
+      counts_add(cnt, P.cnt);
       active = false;
     }
   }
@@ -1240,13 +1182,10 @@ __device__ __forceinline__ void mc_state_load(const McState &s, const RenderArgs
   L.rng.ctr = s.rctr;
   L.iter = s.iter;
 }
-__device__ __forceinline__ void counts_add(Counts &c, const Counts &d) {
-  c.shadow += d.shadow; c.monte += d.monte; c.trans += d.trans;
-  c.spec += d.spec; c.indirect += d.indirect; c.caustic += d.caustic;
-}
 
-// mc_kernel's prologue and the path's first bounce (every path is live there, so the state
-// makes no round trip); the survivors' state is stored and their indices start list 0
+// The prologue and the path's first bounce (every path is live there, so the state makes no
+// round trip); the survivors' state is stored and their indices start list 0 (one atomic per
+// wave; the order of a list's entries is free)
 template <uint32_t KINDS, bool HARD, bool RAYS>
 __global__ __launch_bounds__(128)
 __attribute__((amdgpu_waves_per_eu((HARD && KINDS == KINDS_TRI_SPHERE) ? MC_WAVE_BEGIN_WPE : MC_WPE)))
@@ -1255,52 +1194,15 @@ void mc_wave_begin_kernel(RenderArgs a, McWave w) {
   Counts cnt = {0, 0, 0, 0, 0, 0};
   bool alive = false;
   if (t < a.total_mc) {
-    const SceneView &S = a.S;
-    const Flags &F = a.F;
-    int64_t pb = wave_owner(a.mc_off, a.nprim, t, a.total_mc, a.mc_tab);
-    int s = (int)(t - a.mc_off[pb]);
-    const Spawn &sp = a.spawn[pb];
-    int64_t g = (int64_t)a.path_off[pb] + 1 + s;
-    int pix, i, j, k;
-    uint64_t psample;
-    decode_primary<RAYS>(a, pb, pix, i, j, k, psample);
-    const DMaterial &m = S.mats[sp.mat];
-    V p = ld3(sp.p), n = ld3(sp.n), view = ld3(sp.v);
-    double ct = sp.ct, R = sp.R;
     PathCtx P;
     McLoop L;
-    path_init(P, a, g, pb, 1 + s);  // qstripe: this wave's, (t >> 6) % IND_QS
-    P.hint = sp.tri;
-    Rng rng;
-    V sb;
-    C3 wt;
-    if (s < sp.n_t) {
-      rng.init(F.seed, KIND_TRANS, psample, (uint64_t)s);
-      V ex = transmissive_bounce_nc(F.ir_air, n, view, ct, m.ir);
-      sb = F.distrib_trans ? specular_sample_call(ex, m.n, ct, rng) : ex;
-      wt = ((1.0 - R) * ldc(m.kt)) / (double)sp.n_t;
-      P.cnt.trans++;
-    } else {
-      s -= sp.n_t;
-      rng.init(F.seed, KIND_SPEC, psample, (uint64_t)s);
-      V ex = reflective_bounce(n, view, ct);
-      sb = F.distrib_spec ? specular_sample_call(ex, m.n, ct, rng) : ex;
-      wt = (ldc(m.kt) * R + ldc(m.ks)) / (double)sp.n_s;
-      P.cnt.spec++;
-    }
-    mc_begin(L, p + sb * kEps, sb, rng, wt);
-    if (!F.monte_carlo) L.iter = F.max_monte_depth;  // MonteCarlo_PathTrace returns at once
+    mc_prologue<RAYS>(a, t, P, L);  // qstripe: this wave's, (t >> 6) % IND_QS
     alive = mc_step<KINDS, true, HARD>(P, L);
-    if (alive) {
-      mc_state_store(w.state[t], P, L);
-    } else {
-      a.base[3 * g] = P.base.r;
-      a.base[3 * g + 1] = P.base.g;
-      a.base[3 * g + 2] = P.base.b;
-    }
+    if (alive) mc_state_store(w.state[t], P, L);
+    else store_base(a, P.g, P.base);
     cnt = P.cnt;
   }
-  wave_list_append(w.list[0], w.count, alive, (uint32_t)t);
+  if (alive) w.list[0][wave_take(w.count)] = (uint32_t)t;
   path_stats(a, cnt);
 }
 
@@ -1333,16 +1235,11 @@ void mc_wave_step_kernel(RenderArgs a, McState *state, const uint32_t *in_list,
       } else {
         alive = mc_step<KINDS, true, HARD, true>(P, L);
       }
-      if (alive) {
-        mc_state_store(state[t], P, L);
-      } else {
-        a.base[3 * P.g] = P.base.r;
-        a.base[3 * P.g + 1] = P.base.g;
-        a.base[3 * P.g + 2] = P.base.b;
-      }
+      if (alive) mc_state_store(state[t], P, L);
+      else store_base(a, P.g, P.base);
       counts_add(cnt, P.cnt);
     }
-    wave_list_append(out_list, out_count, alive, t);
+    if (alive) out_list[wave_take(out_count)] = t;
   }
   path_stats(a, cnt);
 }
@@ -1600,14 +1497,7 @@ __device__ __forceinline__ void store_photon(int mode, PhotonOut &o, C3 power, V
     if (mode == PM_EMIT) {
       o.out[o.off + o.count] = ph;
     } else {
-      uint64_t act = __ballot(1);
-      int lane = (int)(threadIdx.x & 63);
-      int leader = __ffsll((long long)act) - 1;
-      uint32_t rank = (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(o.cursor, (uint32_t)__popcll(act));
-      base = (uint32_t)__shfl((int)base, leader, 64);
-      uint32_t slot = base + rank;
+      const uint32_t slot = wave_take(o.cursor);
       if (slot < o.cap) {   // an overflowing launch is re-run with room (trace_batch_dev)
         o.out[slot] = ph;
         o.keys[slot] = (o.j << o.obits) | (uint64_t)o.count;
@@ -1858,6 +1748,27 @@ void launch_primary(const RenderArgs &a, hipStream_t st) {
 void launch_camera_rays(const CameraRaysArgs &a, hipStream_t st) {
   if (a.n > 0) camera_rays_kernel<<<nblk(a.n, 256), 256, 0, st>>>(a);
 }
+// Which instance of a path kernel a scene takes. with_kinds hands f the smallest instantiated
+// element set that holds the scene's kinds, as a std::integral_constant (f is a generic lambda
+// and reads K.value as a template argument). with_kinds_hard adds HARD, true where every light
+// of the scene is a hard one, as a std::bool_constant; there is no HARD instance of KINDS_ALL:
+// a scene outside KINDS_POLY takes the general light loop whatever its lights are.
+template <class F>
+static void with_kinds(const SceneView &S, F f) {
+  if (kinds_within(S.kinds, KINDS_TRI_SPHERE)) f(std::integral_constant<uint32_t, KINDS_TRI_SPHERE>{});
+  else if (kinds_within(S.kinds, KINDS_POLY)) f(std::integral_constant<uint32_t, KINDS_POLY>{});
+  else f(std::integral_constant<uint32_t, KINDS_ALL>{});
+}
+template <class F>
+static void with_kinds_hard(const SceneView &S, F f) {
+  with_kinds(S, [&](auto K) {
+    if constexpr (K.value != KINDS_ALL) {
+      if (S.hard_lights) return f(K, std::true_type{});
+    }
+    f(K, std::false_type{});
+  });
+}
+
 // occupancy: 4 waves per SIMD where the kernel fits 128 VGPRs without spills (triangles and
 // spheres only; C2 ind_kernel 37.8 -> 31.3 ms, frame -2.6 %), else 3 (the 4-wave instances of
 // the other element sets spill 74-129 VGPRs; 3 or 5 waves for triangles and spheres measured
@@ -1869,20 +1780,14 @@ void launch_ind(const RenderArgs &a, unsigned g, hipStream_t st) {
 }
 void launch_cont(const RenderArgs &a, const IndCont *q, const uint32_t *fill, uint32_t cap_s,
                  hipStream_t st) {
-  if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0)
-    ind_cont_kernel<KINDS_TRI_SPHERE><<<IND_QS * 32, 128, 0, st>>>(a, q, fill, cap_s);
-  else if ((a.S.kinds & ~KINDS_POLY) == 0)
-    ind_cont_kernel<KINDS_POLY><<<IND_QS * 32, 128, 0, st>>>(a, q, fill, cap_s);
-  else
-    ind_cont_kernel<KINDS_ALL><<<IND_QS * 32, 128, 0, st>>>(a, q, fill, cap_s);
+  with_kinds(a.S, [&](auto K) {
+    ind_cont_kernel<K.value><<<IND_QS * 32, 128, 0, st>>>(a, q, fill, cap_s);
+  });
 }
 static void launch_mc_sub(const RenderArgs &a, hipStream_t st) {
-  if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0)
-    mc_sub_kernel<KINDS_TRI_SPHERE><<<IND_QS * 32, 128, 0, st>>>(a, a.mc_cont, a.mc_ncont, a.mc_cap_s);
-  else if ((a.S.kinds & ~KINDS_POLY) == 0)
-    mc_sub_kernel<KINDS_POLY><<<IND_QS * 32, 128, 0, st>>>(a, a.mc_cont, a.mc_ncont, a.mc_cap_s);
-  else
-    mc_sub_kernel<KINDS_ALL><<<IND_QS * 32, 128, 0, st>>>(a, a.mc_cont, a.mc_ncont, a.mc_cap_s);
+  with_kinds(a.S, [&](auto K) {
+    mc_sub_kernel<K.value><<<IND_QS * 32, 128, 0, st>>>(a, a.mc_cont, a.mc_ncont, a.mc_cap_s);
+  });
 }
 // The breadth-first Monte Carlo schedule: the begin kernel (prologue + first bounce), rounds - 1
 // launches of one bounce each over the ping-ponged live lists, and one launch that runs the
@@ -1940,35 +1845,17 @@ static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, 
     if (a.mc_cont && a.mc_next) {
       // persistent: enough blocks to fill the chip at MC_WPE waves per SIMD, or one per 128 paths
       unsigned gp = std::min(g, (unsigned)(a.mc_persist_blocks > 0 ? a.mc_persist_blocks : 1024));
-      if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
-        if (a.S.hard_lights) mc_persist_kernel<KINDS_TRI_SPHERE, true, true, RAYS><<<gp, 128, 0, ms>>>(a);
-        else mc_persist_kernel<KINDS_TRI_SPHERE, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
-      } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
-        if (a.S.hard_lights) mc_persist_kernel<KINDS_POLY, true, true, RAYS><<<gp, 128, 0, ms>>>(a);
-        else mc_persist_kernel<KINDS_POLY, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
-      } else {
-        mc_persist_kernel<KINDS_ALL, true, false, RAYS><<<gp, 128, 0, ms>>>(a);
-      }
+      with_kinds_hard(a.S, [&](auto K, auto HARD) {
+        mc_persist_kernel<K.value, true, HARD.value, RAYS><<<gp, 128, 0, ms>>>(a);
+      });
     } else if (wave) {
-      if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
-        if (a.S.hard_lights) launch_mc_wave<KINDS_TRI_SPHERE, true, RAYS>(a, *mw, ms);
-        else launch_mc_wave<KINDS_TRI_SPHERE, false, RAYS>(a, *mw, ms);
-      } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
-        if (a.S.hard_lights) launch_mc_wave<KINDS_POLY, true, RAYS>(a, *mw, ms);
-        else launch_mc_wave<KINDS_POLY, false, RAYS>(a, *mw, ms);
-      } else {
-        launch_mc_wave<KINDS_ALL, false, RAYS>(a, *mw, ms);
-      }
+      with_kinds_hard(a.S, [&](auto K, auto HARD) {
+        launch_mc_wave<K.value, HARD.value, RAYS>(a, *mw, ms);
+      });
     } else if (a.mc_cont) {
-      if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) {
-        if (a.S.hard_lights) mc_kernel<KINDS_TRI_SPHERE, true, true, RAYS><<<g, 128, 0, ms>>>(a);
-        else mc_kernel<KINDS_TRI_SPHERE, true, false, RAYS><<<g, 128, 0, ms>>>(a);
-      } else if ((a.S.kinds & ~KINDS_POLY) == 0) {
-        if (a.S.hard_lights) mc_kernel<KINDS_POLY, true, true, RAYS><<<g, 128, 0, ms>>>(a);
-        else mc_kernel<KINDS_POLY, true, false, RAYS><<<g, 128, 0, ms>>>(a);
-      } else {
-        mc_kernel<KINDS_ALL, true, false, RAYS><<<g, 128, 0, ms>>>(a);
-      }
+      with_kinds_hard(a.S, [&](auto K, auto HARD) {
+        mc_kernel<K.value, true, HARD.value, RAYS><<<g, 128, 0, ms>>>(a);
+      });
     }
     if (a.mc_cont) {
       if (a.mc_cont2) {
@@ -1984,9 +1871,7 @@ static void launch_path_t(const RenderArgs &a, hipStream_t st, hipStream_t st2, 
   if (a.total_ind > 0) {
     unsigned g = nblk(a.tind, 128);
     if (!a.split_ind) ind_kernel<2, false, KINDS_ALL, RAYS><<<g, 128, 0, st>>>(a);
-    else if ((a.S.kinds & ~KINDS_TRI_SPHERE) == 0) launch_ind<KINDS_TRI_SPHERE, RAYS>(a, g, st);
-    else if ((a.S.kinds & ~KINDS_POLY) == 0) launch_ind<KINDS_POLY, RAYS>(a, g, st);
-    else launch_ind<KINDS_ALL, RAYS>(a, g, st);
+    else with_kinds(a.S, [&](auto K) { launch_ind<K.value, RAYS>(a, g, st); });
     // continuations: 32 blocks per stripe stride over its fill
     if (a.split_ind) launch_cont(a, a.ind_cont, a.ind_ncont, a.ind_cap_s, st);
   }
