@@ -3,6 +3,7 @@
 // adaptive passes and reprojection, tone mapping.
 #include <cmath>
 #include <functional>
+#include <limits>
 #include "gi_ctx.h"
 #include "gi_denoise.h"
 #include "gi_radiance.h"
@@ -976,6 +977,64 @@ int gi_accum_denoise(gi_ctx *c, const gi_pixel_features *feat, const gi_vdenoise
                              c->s.dn_img[0].as<float4>(), c->stream);
   HIPCHK(c, hipGetLastError());
   return vdenoise_levels(c, c->acc_w, c->acc_h, feat, P, out_mean, out_vlum, kernel_ms);
+}
+
+void gi_progressive_params_default(gi_progressive_params *p) {
+  if (!p) return;
+  p->alpha = 0.7;
+  p->global_radius = 0.0;
+  p->caustic_radius = 0.0;
+}
+
+// Knaus & Zwicker's radius schedule, r_{j+1}^2 = r_j^2 (j + alpha) / (j + 1) with j counted from 1:
+// host arithmetic, one IEEE operation per step (tests/progressive_ref.py restates it)
+double gi_progressive_radius(double r0, double alpha, int64_t pass) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (!(r0 > 0.0) || !std::isfinite(r0) || !(alpha > 0.0 && alpha < 1.0) || pass < 0 ||
+      pass >= ((int64_t)1 << 20))
+    return nan;
+  double r2 = r0 * r0;
+  for (int64_t j = 1; j <= pass; j++) r2 = (r2 * ((double)j + alpha)) / ((double)j + 1.0);
+  return std::sqrt(r2);
+}
+
+int gi_accum_add_progressive(gi_ctx *c, int aa, int64_t pass, const gi_progressive_params *pp,
+                             gi_photon_stats *pstats, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "progressive passes are for one-device contexts");
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded (gi_read_scene)");
+  int rc = check_accum(c);
+  if (rc) return rc;
+  gi_progressive_params D;
+  gi_progressive_params_default(&D);
+  if (pp) D = *pp;
+  const gi_params P = c->P;
+  if (P.irradiance_cache)
+    return fail(c, GI_ERR_ARG, "progressive passes do not take the irradiance cache");
+  if (aa < 0 || aa > 15) return fail(c, GI_ERR_ARG, "bad image size");
+  if (pass < 0 || pass >= ((int64_t)1 << 20))
+    return fail(c, GI_ERR_ARG, "progressive pass index must be in [0, 2^20)");
+  if (!(D.alpha > 0.0 && D.alpha < 1.0))
+    return fail(c, GI_ERR_ARG, "progressive alpha must be inside (0, 1)");
+  const double r0g = D.global_radius == 0.0 ? P.global_estimate_dist : D.global_radius;
+  const double r0c = D.caustic_radius == 0.0 ? P.caustic_estimate_dist : D.caustic_radius;
+  const double rg = gi_progressive_radius(r0g, D.alpha, pass);
+  const double rcst = gi_progressive_radius(r0c, D.alpha, pass);
+  if (std::isnan(rg) || std::isnan(rcst))
+    return fail(c, GI_ERR_ARG, "progressive radii must be finite and positive");
+  gi_params Q = P;
+  Q.seed = P.seed + (uint64_t)pass;
+  Q.global_estimate_size = GI_ESTIMATE_ALL;
+  Q.caustic_estimate_size = GI_ESTIMATE_ALL;
+  Q.global_estimate_dist = rg;
+  Q.caustic_estimate_dist = rcst;
+  rc = gi_set_params(c, &Q);
+  if (!rc) rc = gi_map_photons(c, pstats);
+  if (!rc) rc = gi_accum_add_image(c, aa, st);
+  // the context's own parameters come back whatever happened; the maps stay the pass's
+  const int rc2 = gi_set_params(c, &P);
+  return rc ? rc : rc2;
 }
 
 int gi_tonemap(gi_ctx *c, int w, int h, const float *radiance, double exposure, double white,

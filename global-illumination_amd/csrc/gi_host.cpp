@@ -117,16 +117,23 @@ int ensure_dk(gi_ctx *c, KnnArgs &k) {
 //   8  large-K chunk kernel + query-per-wave fallback (K > 64, estimates; needs dk bounds)
 //   1  query-per-wave kernel (K + 64 <= 1024)
 //   0  per-lane kernel with global-memory heaps (any K)
+//  10  fixed-radius range estimate (gi_range.hip; estimates with K above the map's photon count:
+//      no query reaches K, so nothing is selected). Automatic where only kind 0 served before.
 static int knn_kind(const gi_ctx *c, const KnnArgs &k) {
   int kind = c->knn_kernel_kind;
   const bool list = k.mode == KNN_MODE_LIST, dkm = k.mode == KNN_MODE_DK;
+  const bool wide = (int64_t)k.K + 64 > 1024;  // beyond the LDS selection kernels
+  const bool range_ok = !list && !dkm && (int64_t)k.K > k.map.n;
   int auto_kind = (k.K <= 64) ? (list ? 3 : 7) : ((list || !c->use_dk) ? 1 : 8);
+  if (range_ok && wide) auto_kind = 10;
   if (kind < 0) kind = auto_kind;
   // an override that cannot serve this launch falls back to the automatic choice
+  if (kind == 10 && !range_ok) kind = auto_kind;
+  if (kind == 10) return kind;
   if (kind == 7 && (k.K > 64 || list)) kind = auto_kind;
-  if (kind == 8 && (list || dkm || k.K + 64 > 1024 || !c->use_dk)) kind = auto_kind == 8 ? 1 : auto_kind;
+  if (kind == 8 && (list || dkm || wide || !c->use_dk)) kind = auto_kind == 8 ? 1 : auto_kind;
   if (kind == 3 && (size_t)k.K * 512 > 64 * 1024) kind = auto_kind;
-  if (kind == 1 && k.K + 64 > 1024) kind = 0;
+  if (kind == 1 && wide) kind = 0;
   return kind;
 }
 
@@ -259,6 +266,17 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
   const hipStream_t st = X.st;
   const int kind = knn_kind(c, k);
   if (k.mode != KNN_MODE_DK) c->last_kind[map_index(k)] = kind;
+  if (kind == 10) {
+    // fixed-radius range estimate: one launch, no dk bounds, no fallback
+    k.nq = nq;
+    k.q0 = 0;
+    k.map.dk = nullptr;
+    HIPCHK(c, hipEventRecord(X.ev0, X.st));
+    if (!launch_knn_range(k, X.st))
+      return fail(c, GI_ERR_ARG, "k-NN launch: the range estimate needs an estimate size above the map");
+    HIPCHK(c, hipGetLastError());
+    return knn_end(c, X, ms);
+  }
   if (kind == 8) {
     // large-K chunk kernel, then the query-per-wave kernel on what it hands over
     int rc = ensure_dk(c, k);

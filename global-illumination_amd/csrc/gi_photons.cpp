@@ -554,7 +554,8 @@ int gi_map_photons(gi_ctx *c, gi_photon_stats *st) {
     for (int m = 0; m < 2; m++) {
       if (!d->map_valid[m] || d->res.dmap[m].n == 0) continue;
       KnnArgs k = knn_args(d, m);
-      if (k.K <= 0 || k.K + 64 > 1024) continue;  // only the per-lane global-heap kernel
+      // beyond the LDS kernels: the per-lane global-heap kernel or the range estimate, no bounds
+      if (k.K <= 0 || (int64_t)k.K + 64 > 1024) continue;
       int r = ensure_dk(d, k);
       if (r) return r;
     }

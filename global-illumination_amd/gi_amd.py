@@ -59,6 +59,7 @@ EXPORTED = [
     "gi_get_view", "gi_reproject_params_default", "gi_accum_reproject",
     "gi_accum_export", "gi_accum_import", "gi_accum_merge", "gi_accum_export_packed",
     "gi_accum_merge_packed", "gi_accum_merge_from",
+    "gi_progressive_params_default", "gi_progressive_radius", "gi_accum_add_progressive",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
@@ -136,6 +137,15 @@ class ReprojectStats(C.Structure):
     """gi_reproject_stats"""
     _fields_ = [("kept_pixels", C.c_int64), ("reset_pixels", C.c_int64),
                 ("kept_samples", C.c_int64)]
+
+
+class ProgressiveParams(C.Structure):
+    """gi_progressive_params"""
+    _fields_ = [("alpha", C.c_double), ("global_radius", C.c_double),
+                ("caustic_radius", C.c_double)]
+
+
+GI_ESTIMATE_ALL = 1 << 30
 
 
 class AdaptiveParams(C.Structure):
@@ -287,6 +297,13 @@ def lib():
         L.gi_accum_merge_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                             P(C.c_double)]
         L.gi_accum_merge_from.argtypes = [C.c_void_p, C.c_void_p, P(C.c_double)]
+        L.gi_progressive_params_default.argtypes = [P(ProgressiveParams)]
+        L.gi_progressive_params_default.restype = None
+        L.gi_progressive_radius.argtypes = [C.c_double, C.c_double, C.c_int64]
+        L.gi_progressive_radius.restype = C.c_double
+        L.gi_accum_add_progressive.argtypes = [C.c_void_p, C.c_int, C.c_int64,
+                                               P(ProgressiveParams), P(PhotonStats),
+                                               P(RenderStats)]
         L.gi_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                  C.c_double, C.c_void_p, C.c_void_p]
         L.gi_radiance_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -353,6 +370,24 @@ def adaptive_params(**kw):
             raise TypeError(f"unknown adaptive parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def progressive_params(**kw):
+    """gi_progressive_params: the defaults (gi_progressive_params_default) with the given fields
+    set."""
+    p = ProgressiveParams()
+    lib().gi_progressive_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(ProgressiveParams._fields_):
+            raise TypeError(f"unknown progressive parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def progressive_radius(r0, alpha, npass):
+    """The radius of progressive pass `npass` (0-based) from r0 (gi_progressive_radius); NaN for
+    a bad argument."""
+    return lib().gi_progressive_radius(float(r0), float(alpha), int(npass))
 
 
 def ParseArgs(argv):
@@ -620,6 +655,16 @@ class Renderer:
         st = RenderStats()
         self._check(lib().gi_accum_add_image(self._ctx, aa, C.byref(st)))
         return _stats_dict(st)
+
+    def accum_add_progressive(self, aa, npass, params=None, **kw):
+        """Progressive photon-map pass `npass` (0-based) into the accumulator
+        (gi_accum_add_progressive): fresh maps under seed + npass, fixed-radius estimates at the
+        pass's radii. Returns (photon stats, render stats)."""
+        p = params if params is not None else progressive_params(**kw)
+        pst, st = PhotonStats(), RenderStats()
+        self._check(lib().gi_accum_add_progressive(self._ctx, aa, npass, C.byref(p),
+                                                   C.byref(pst), C.byref(st)))
+        return {f: getattr(pst, f) for f, _ in PhotonStats._fields_}, _stats_dict(st)
 
     def accum_add_rays(self, spp, rays, ids=None):
         """Render one ray pass of the accumulator's size and fold it in (gi_accum_add_rays); give

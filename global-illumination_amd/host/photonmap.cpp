@@ -37,6 +37,12 @@
 // -1. -noise T is tested after a pass, as without a file: a resumed run renders at least one pass,
 // also when the loaded state is already at T (the uninterrupted run would have stopped there, and
 // its file would not have been resumed).
+// Extension: -progressive A (A in (0, 1); a radiance flag, with -passes / -noise): progressive
+// photon mapping. No maps are built up front; pass i is gi_accum_add_progressive with the index
+// passes_done + i: fresh maps of -global / -caustic photons under seed + index, fixed-radius
+// estimates whose radii shrink from -gd / -cd by the schedule of gi_progressive_radius. Refused
+// before a device is opened with -adaptive, -views, -cache or -gpus N. The accumulator file does
+// not record the flag: a resumed run must be given the same -progressive A.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -154,6 +160,8 @@ struct RadianceFlags {
   double noise = 0.0, exposure = 1.0, white = 0.0;
   const char *file = nullptr;
   const char *save_accum = nullptr, *load_accum = nullptr;
+  bool progressive = false;  // -progressive A: fresh photon maps and a shrinking fixed radius per pass
+  double alpha = 0.0;
 };
 // null, or the flag that is malformed
 static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
@@ -200,6 +208,14 @@ static const char *TakeRadiance(int &argc, char **argv, RadianceFlags &r) {
   if (!TakeValue(argc, argv, "-save_accum", &r.save_accum)) return "-save_accum";
   if (!TakeValue(argc, argv, "-load_accum", &r.load_accum)) return "-load_accum";
   if (r.save_accum || r.load_accum) r.any = true;
+  t = nullptr;
+  if (!TakeValue(argc, argv, "-progressive", &t)) return "-progressive";
+  if (t) {
+    if (!ParseNumber(t, &v) || !(v > 0.0 && v < 1.0)) return "-progressive";
+    if (r.adaptive_tile) return "-progressive (not with -adaptive)";
+    r.alpha = v;
+    r.progressive = r.any = true;
+  }
   if (r.adaptive_tile && !r.have_noise) return "-adaptive";
   if (r.passes == 0) r.passes = r.have_noise ? 4096 : 1;
   return nullptr;
@@ -361,6 +377,10 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Invalid program argument: -views (not with -save_accum or -load_accum)\n");
     return -1;
   }
+  if (views_file && rad.progressive) {
+    fprintf(stderr, "Invalid program argument: -progressive (not with -views)\n");
+    return -1;
+  }
   if (views_file) {
     if (denoise_levels) {
       fprintf(stderr, "Invalid program argument: -views (not with -denoise)\n");
@@ -410,6 +430,14 @@ int main(int argc, char **argv) {
     }
     if (ds.count == 0) ds.count = 1;
   }
+  if (rad.progressive && P.irradiance_cache) {
+    fprintf(stderr, "Invalid program argument: -progressive (not with -cache)\n");
+    return -1;
+  }
+  if (rad.progressive && ds.count > 1) {
+    fprintf(stderr, "-progressive renders on one device: not with -gpus %d\n", ds.count);
+    return -1;
+  }
   if (rad.any && ds.count > 1) {
     fprintf(stderr, "-passes, -noise, -exposure, -white, -radiance, -vdenoise and -views render on one device: not with -gpus %d\n",
             ds.count);
@@ -452,7 +480,8 @@ int main(int argc, char **argv) {
     printf("  # Lights = %d\n", nl);
     fflush(stdout);
   }
-  if (P.indirect_illum || P.caustic_illum || P.direct_photon_illum) {
+  // -progressive: every pass builds its own maps
+  if (!rad.progressive && (P.indirect_illum || P.caustic_illum || P.direct_photon_illum)) {
     gi_photon_stats ps;
     if (gi_map_photons(ctx, &ps) != GI_OK) {
       fprintf(stderr, "%s\n", gi_last_error(ctx));
@@ -531,6 +560,25 @@ int main(int argc, char **argv) {
         Pi.seed = P.seed + (uint64_t)loaded.passes_done + (uint64_t)i;
         gi_render_stats ps;
         prog.last[0] = -1;
+        if (rad.progressive) {
+          // pass index = the seed offset; r_0 from -gd / -cd, photons per pass from -global / -caustic
+          const int64_t idx = loaded.passes_done + (int64_t)i;
+          gi_progressive_params pp;
+          gi_progressive_params_default(&pp);
+          pp.alpha = rad.alpha;
+          gi_photon_stats pst;
+          ok = gi_set_params(ctx, &P) == GI_OK &&
+               gi_accum_add_progressive(ctx, aa, idx, &pp, &pst, &ps) == GI_OK;
+          if (!ok) break;
+          if (P.verbose) {
+            printf("Progressive pass %lld: -gd %.17g -cd %.17g, %lld global and %lld caustic photons stored\n",
+                   (long long)idx, gi_progressive_radius(P.global_estimate_dist, rad.alpha, idx),
+                   gi_progressive_radius(P.caustic_estimate_dist, rad.alpha, idx),
+                   (long long)pst.global_stored, (long long)pst.caustic_stored);
+            fflush(stdout);
+          }
+          primary_samples += ((long long)w * h) << (2 * aa);
+        } else {
         ok = gi_set_params(ctx, &Pi) == GI_OK;
         // a carried accumulator goes straight to adaptive passes: the selection's n_min < min_samples
         // rule makes the tiles whose history was lost core
@@ -542,6 +590,7 @@ int main(int argc, char **argv) {
         } else if (ok) {
           ok = gi_accum_add_image(ctx, aa, &ps) == GI_OK;
           primary_samples += ((long long)w * h) << (2 * aa);
+        }
         }
         if (!ok) break;
         passes_done++;

@@ -50,6 +50,9 @@ enum {
 
 enum { GI_FILTER_DISK = 0, GI_FILTER_CONE = 1, GI_FILTER_GAUSS = 2 }; /* render.h Filter_Type */
 enum { GI_MAP_GLOBAL = 0, GI_MAP_CAUSTIC = 1 };                      /* render.h Photon_Type */
+/* an estimate size no map reaches: every estimate is a fixed-radius one (all photons within the
+ * estimate distance, normalised by that distance, as EstimateRadiance does below K photons) */
+#define GI_ESTIMATE_ALL (1 << 30)
 
 /* ---- parameters: one field per reference global (photonmap.cpp:40-106, render.h:27-81) -- */
 typedef struct gi_params {
@@ -147,7 +150,8 @@ typedef struct gi_render_stats {
   uint64_t knn_map_fallback_queries[2];
   /* k-NN launch sequence the last batch ran per map (-1 none): 7 lane-select chunk kernel +
    * per-lane fallback, 8 large-K chunk kernel (+ second chunk pass) + query-per-wave fallback,
-   * 3 per-lane, 1 query-per-wave, 0 per-lane with global heaps, 9 irradiance-cache lookup */
+   * 3 per-lane, 1 query-per-wave, 0 per-lane with global heaps, 9 irradiance-cache lookup,
+   * 10 fixed-radius range estimate (estimate size above the map's photon count) */
   int32_t knn_map_kind[2];
   /* chunk k-NN path: time of the second chunk pass (larger LDS candidate set) and the queries
    * the first pass handed to it (those it did not resolve are in knn_map_fallback_queries) */
@@ -438,6 +442,37 @@ int gi_accum_merge_packed(gi_ctx *ctx, int nstates, const void *packed /* DEVICE
  * state is copied to the destination's device and folded there; src is left bit for bit
  * unchanged. */
 int gi_accum_merge_from(gi_ctx *dst, gi_ctx *src, double *kernel_ms /* optional */);
+
+/* ---- progressive photon-map passes (Knaus & Zwicker 2011, the probabilistic form) ------------
+ * Every pass traces fresh photon maps under its own seed, estimates with a fixed radius that
+ * shrinks by a global schedule, and is averaged by the accumulator (DESIGN.md "Fixed-radius
+ * estimate and progressive passes"). No reference counterpart; tests/progressive_ref.py restates
+ * the schedule. */
+typedef struct gi_progressive_params {
+  double alpha;           /* in (0, 1); default 0.7 */
+  double global_radius;   /* r_0 > 0 and finite; 0 = the context's global_estimate_dist */
+  double caustic_radius;  /* likewise, caustic_estimate_dist */
+} gi_progressive_params;
+void gi_progressive_params_default(gi_progressive_params *p);
+/* The radius of pass `pass` (0-based). Host only, one IEEE operation per step:
+ *   r2 = r0 * r0; for j = 1 .. pass: r2 = (r2 * ((double)j + alpha)) / ((double)j + 1.0);
+ *   return sqrt(r2).
+ * NaN for r0 <= 0 or not finite, alpha outside (0, 1), pass < 0 or pass >= 2^20. */
+double gi_progressive_radius(double r0, double alpha, int64_t pass);
+/* Pass `pass`, defined as this sequence of calls, bit for bit: with P the context's parameters
+ * and Q = P with seed = P.seed + pass, both estimate sizes GI_ESTIMATE_ALL and both estimate
+ * distances gi_progressive_radius(r_0, alpha, pass):
+ *   gi_set_params(Q); gi_map_photons (pstats); gi_accum_add_image(aa) (stats); gi_set_params(P).
+ * The maps stay the pass's. On failure P is restored and the accumulator is as the failed step
+ * left it. The schedule depends on the pass index alone, so a saved accumulator resumes with the
+ * index it stopped at. GI_ERR_UNSUPPORTED on a device set; GI_ERR_STATE before a scene or before
+ * gi_accum_reset / gi_accum_import; GI_ERR_ARG for a bad parameter, a pass out of range, or
+ * irradiance_cache set (the cache bakes a K-estimate into the map). A refused call changes
+ * nothing. */
+int gi_accum_add_progressive(gi_ctx *ctx, int aa, int64_t pass,
+                             const gi_progressive_params *p /* NULL: defaults */,
+                             gi_photon_stats *pstats /* optional */,
+                             gi_render_stats *stats /* optional */);
 
 /* ---- adaptive passes: refine only the noisy tiles of the accumulator --------------------- */
 /* The accumulator's frame is cut into tiles of tile_px x tile_px pixels: tiles_x = ceil(W /
