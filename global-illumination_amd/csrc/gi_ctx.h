@@ -140,6 +140,9 @@ struct Scratch {
   // radiance frames: rad_frame holds the pass's {m, M2} (six doubles per pixel), rad_samples the
   // samples when the caller asked for them
   DBuf rad_frame, rad_samples, rad_mean, rad_var;
+  // light-path layers (gi.h GI_LAYER_*), layer-major: the batch's per-primary sums, the frame's
+  // {m, M2} planes and, when asked for, its samples
+  DBuf prim_layers, lay_frame, lay_samples;
   DBuf acc_part;                        // per-block partial sums of the accumulator's reductions
   DBuf tile_err, tile_nmin, tile_mask;  // adaptive passes: per tile error, smallest count, mask
   DBuf rp_prev, rp_cur;                 // reprojection: the two uploaded plane sets
@@ -264,6 +267,12 @@ struct gi_ctx {
   // radiance frames (gi_render_radiance, gi_render_rays_radiance, gi_accum_add_*): while rad_on,
   // render_pixels launches reduce_radiance_kernel beside reduce_kernel
   bool rad_on = false, rad_want_samples = false;
+  // ... and, while lay_on, reduce_prim_layers_kernel and one reduce_radiance_kernel per layer
+  // into s.lay_frame (lay_npix pixels per plane). lay_time: the kernel between two events, waited
+  // for per batch and summed into lay_ms (gi_layers_timing)
+  bool lay_on = false, lay_time = false;
+  size_t lay_npix = 0;
+  double lay_ms = 0.0;
   // accumulator over passes (res.acc, res.acc_cnt): state of the context, kept by
   // gi_release_scratch. While only whole-frame passes were folded (acc_uniform) every count is acc_n.
   int acc_w = 0, acc_h = 0;

@@ -189,9 +189,11 @@ int gi_denoise(gi_ctx *c, int w, int h, const float *rgbf, const gi_pixel_featur
 // every pixel, a batch re-run under the slot guard never reached its reduction).
 // pix (camera passes only): render these output pixels instead of the whole frame; rad_frame keeps
 // what it held at the others.
+// layers (whole frames only): the light-path layers' {m, M2} planes into c->s.lay_frame as well
+// (and their samples into c->s.lay_samples), under rad_frame's contract.
 static int radiance_pass(gi_ctx *c, int aa, int w, int h, bool want_samples, gi_render_stats *st,
                          const RaySrc *rsrc, int64_t *S_out,
-                         const std::vector<int32_t> *pix = nullptr) {
+                         const std::vector<int32_t> *pix = nullptr, bool layers = false) {
   hipSetDevice(c->device);
   int rc = check_ready(c);
   if (rc) return rc;
@@ -202,18 +204,25 @@ static int radiance_pass(gi_ctx *c, int aa, int w, int h, bool want_samples, gi_
     return fail(c, GI_ERR_ARG, "width * height * samples per pixel must be below 2^31");
   HIPCHK(c, c->s.rad_frame.ensure(npix * 48));
   if (want_samples) HIPCHK(c, c->s.rad_samples.ensure(npix * (size_t)S * 24));
+  if (layers) {
+    HIPCHK(c, c->s.lay_frame.ensure(GI_LAYER_COUNT * npix * 48));
+    if (want_samples) HIPCHK(c, c->s.lay_samples.ensure(GI_LAYER_COUNT * npix * (size_t)S * 24));
+    c->lay_npix = npix;
+  }
   c->rad_want_samples = want_samples;
+  c->lay_on = layers;
   c->rad_on = true;
   rc = pix ? render_common(c, aa, w, h, *pix, nullptr, nullptr, st, false)
            : render_frame(c, aa, w, h, nullptr, nullptr, st, rsrc);
   c->rad_on = false;
+  c->lay_on = false;
   *S_out = S;
   return rc;
 }
 
 // {m, M2} of n samples per pixel (counts: of counts[p], the accumulator's) -> host float mean /
 // variance of the mean (either may be null)
-static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n, float *mean,
+static int radiance_resolve(gi_ctx *c, const double *frame, size_t npix, int64_t n, float *mean,
                             float *variance, const int64_t *counts = nullptr) {
   if (!mean && !variance) return GI_OK;
   HIPCHK(c, c->s.rad_mean.ensure(npix * 12));
@@ -223,7 +232,7 @@ static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n
   a.npix = (int64_t)npix;
   a.n = n;
   a.counts = counts;
-  a.frame = (const double *)frame.p;
+  a.frame = frame;
   a.mean = mean ? c->s.rad_mean.as<float>() : nullptr;
   a.variance = variance ? c->s.rad_var.as<float>() : nullptr;
   launch_radiance_resolve(a, c->stream);
@@ -235,21 +244,34 @@ static int radiance_resolve(gi_ctx *c, const DBuf &frame, size_t npix, int64_t n
   return GI_OK;
 }
 
+// layers: the outputs hold GI_LAYER_COUNT + 1 planes, the layers' and then the frame's own
 static int render_radiance(gi_ctx *c, int aa, int w, int h, const RaySrc *rsrc, float *mean,
-                           float *variance, double *samples, gi_render_stats *st) {
+                           float *variance, double *samples, gi_render_stats *st,
+                           bool layers = false) {
   if (!c->peers.empty())
     return fail(c, GI_ERR_UNSUPPORTED, "radiance frames are for one-device contexts");
   if (!mean && !variance && !samples) return fail(c, GI_ERR_ARG, "null image buffer");
   int64_t S = 0;
-  int rc = radiance_pass(c, aa, w, h, samples != nullptr, st, rsrc, &S);
+  int rc = radiance_pass(c, aa, w, h, samples != nullptr, st, rsrc, &S, nullptr, layers);
   if (rc) return rc;
   const size_t npix = (size_t)w * h;
+  const size_t nsmp = npix * (size_t)S * 3;  // doubles of one plane of samples
+  const int total = layers ? GI_LAYER_TOTAL : 0;
   if (samples) {
-    HIPCHK(c, hipMemcpyAsync(samples, c->s.rad_samples.p, npix * (size_t)S * 24, hipMemcpyDeviceToHost,
+    if (layers)
+      HIPCHK(c, hipMemcpyAsync(samples, c->s.lay_samples.p, GI_LAYER_COUNT * nsmp * 8,
+                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(samples + total * nsmp, c->s.rad_samples.p, nsmp * 8, hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  return radiance_resolve(c, c->s.rad_frame, npix, S, mean, variance);
+  for (int l = 0; l < total; l++) {
+    rc = radiance_resolve(c, c->s.lay_frame.as<double>() + l * npix * 6, npix, S,
+                          mean ? mean + l * npix * 3 : nullptr, variance ? variance + l * npix * 3 : nullptr);
+    if (rc) return rc;
+  }
+  return radiance_resolve(c, c->s.rad_frame.as<double>(), npix, S, mean ? mean + total * npix * 3 : nullptr,
+                          variance ? variance + total * npix * 3 : nullptr);
 }
 
 // gi_render_rays' argument checks
@@ -278,6 +300,31 @@ int gi_render_rays_radiance(gi_ctx *c, int w, int h, int spp, const gi_ray *rays
   if (rc) return rc;
   const RaySrc src{rays, ids, spp};
   return render_radiance(c, 0, w, h, &src, mean, variance, samples, st);
+}
+
+int gi_render_layers(gi_ctx *c, int aa, int w, int h, float *mean, float *variance, double *samples,
+                     gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  return render_radiance(c, aa, w, h, nullptr, mean, variance, samples, st, true);
+}
+
+int gi_render_rays_layers(gi_ctx *c, int w, int h, int spp, const gi_ray *rays, const uint64_t *ids,
+                          float *mean, float *variance, double *samples, gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->peers.empty())
+    return fail(c, GI_ERR_UNSUPPORTED, "radiance frames are for one-device contexts");
+  int rc = check_ray_args(c, w, h, spp, rays);
+  if (rc) return rc;
+  const RaySrc src{rays, ids, spp};
+  return render_radiance(c, 0, w, h, &src, mean, variance, samples, st, true);
+}
+
+int gi_layers_timing(gi_ctx *c, int on, double *ms) {
+  if (!c) return GI_ERR_ARG;
+  if (ms) *ms = c->lay_ms;
+  c->lay_time = on != 0;
+  if (on) c->lay_ms = 0.0;
+  return GI_OK;
 }
 
 int gi_accum_reset(gi_ctx *c, int w, int h) {
@@ -313,12 +360,33 @@ static int check_accum(gi_ctx *c) {
   return GI_OK;
 }
 
-// one finished pass (c->s.rad_frame, S samples per pixel) into the accumulator
-static int accum_pass(gi_ctx *c, int aa, const RaySrc *rsrc, gi_render_stats *st) {
+// the layer contexts of a layered pass (gi.h): checked before anything is rendered
+static int check_layer_ctxs(gi_ctx *c, gi_ctx *const *layers) {
+  if (!layers) return fail(c, GI_ERR_ARG, "layers: null context list");
+  for (int l = 0; l < GI_LAYER_COUNT; l++) {
+    gi_ctx *L = layers[l];
+    if (!L) continue;
+    if (L == c) return fail(c, GI_ERR_ARG, "layers: a layer context is the rendering context");
+    for (int m = 0; m < l; m++)
+      if (layers[m] == L) return fail(c, GI_ERR_ARG, "layers: a layer context is listed twice");
+    if (!L->peers.empty() || L->device != c->device)
+      return fail(c, GI_ERR_ARG, "layers: a layer context is a one-device context on the same device");
+    if (!L->acc_valid) return fail(c, GI_ERR_STATE, "a layer context has no accumulator (gi_accum_reset)");
+    if (L->acc_w != c->acc_w || L->acc_h != c->acc_h)
+      return fail(c, GI_ERR_ARG, "layers: a layer context's accumulator is not the accumulator's size");
+  }
+  return GI_OK;
+}
+
+// one finished pass (c->s.rad_frame, S samples per pixel) into the accumulator; layers (optional):
+// its layer planes (c->s.lay_frame) by the same update into those contexts' accumulators, which
+// live on this device (every accumulator call ends synchronised, so this stream may write them)
+static int accum_pass(gi_ctx *c, int aa, const RaySrc *rsrc, gi_render_stats *st,
+                      gi_ctx *const *layers = nullptr) {
   int rc = check_accum(c);
   if (rc) return rc;
   int64_t S = 0;
-  rc = radiance_pass(c, aa, c->acc_w, c->acc_h, false, st, rsrc, &S);
+  rc = radiance_pass(c, aa, c->acc_w, c->acc_h, false, st, rsrc, &S, nullptr, layers != nullptr);
   if (rc) return rc;
   AccumArgs a;
   memset(&a, 0, sizeof a);
@@ -329,8 +397,19 @@ static int accum_pass(gi_ctx *c, int aa, const RaySrc *rsrc, gi_render_stats *st
   a.counts = c->res.acc_cnt.as<int64_t>();
   launch_accum_merge(a, c->stream);
   HIPCHK(c, hipGetLastError());
+  for (int l = 0; layers && l < GI_LAYER_COUNT; l++) {
+    gi_ctx *L = layers[l];
+    if (!L) continue;
+    a.pass = c->s.lay_frame.as<double>() + (size_t)l * a.npix * 6;
+    a.acc = L->res.acc.as<double>();
+    a.counts = L->res.acc_cnt.as<int64_t>();
+    launch_accum_merge(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->acc_n += S;  // every pixel's count while acc_uniform, else unused
+  for (int l = 0; layers && l < GI_LAYER_COUNT; l++)
+    if (layers[l]) layers[l]->acc_n += S;
   return GI_OK;
 }
 
@@ -347,6 +426,26 @@ int gi_accum_add_rays(gi_ctx *c, int spp, const gi_ray *rays, const uint64_t *id
   if (rc) return rc;
   const RaySrc src{rays, ids, spp};
   return accum_pass(c, 0, &src, st);
+}
+
+int gi_accum_add_image_layers(gi_ctx *c, int aa, gi_ctx *const layers[GI_LAYER_COUNT],
+                              gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (!rc) rc = check_layer_ctxs(c, layers);
+  if (rc) return rc;
+  return accum_pass(c, aa, nullptr, st, layers);
+}
+
+int gi_accum_add_rays_layers(gi_ctx *c, int spp, const gi_ray *rays, const uint64_t *ids,
+                             gi_ctx *const layers[GI_LAYER_COUNT], gi_render_stats *st) {
+  if (!c) return GI_ERR_ARG;
+  int rc = check_accum(c);
+  if (!rc) rc = check_layer_ctxs(c, layers);
+  if (!rc) rc = check_ray_args(c, c->acc_w, c->acc_h, spp, rays);
+  if (rc) return rc;
+  const RaySrc src{rays, ids, spp};
+  return accum_pass(c, 0, &src, st, layers);
 }
 
 // smallest and summed per-pixel sample count of the accumulator (either output optional)
@@ -722,7 +821,7 @@ int gi_accum_get(gi_ctx *c, float *mean, float *variance, int64_t *nsamples, dou
       if ((rc = count_stats(c, nsamples, nullptr))) return rc;
     }
   }
-  rc = radiance_resolve(c, c->res.acc, npix, 0, mean, variance, c->res.acc_cnt.as<int64_t>());
+  rc = radiance_resolve(c, c->res.acc.as<double>(), npix, 0, mean, variance, c->res.acc_cnt.as<int64_t>());
   if (rc || !noise) return rc;
   const size_t nb = (npix + NOISE_BLOCK - 1) / NOISE_BLOCK;
   HIPCHK(c, c->s.acc_part.ensure(nb * 8));

@@ -767,7 +767,8 @@ static int order_appends(gi_ctx *c, RenderArgs &a, Batch &B) {
   return GI_OK;
 }
 
-// the batch's pixels into the frame's images and, while rad_on, into the radiance frame
+// the batch's pixels into the frame's images and, while rad_on, into the radiance frame (while
+// lay_on too, into the layer frames)
 static int reduce(gi_ctx *c, RenderArgs &a, Batch &B) {
   a.rgbf = c->s.rgbf.as<float>();
   a.rgb8 = c->s.rgb8.as<uint8_t>();
@@ -789,6 +790,41 @@ static int reduce(gi_ctx *c, RenderArgs &a, Batch &B) {
     ra.samples = c->rad_want_samples ? c->s.rad_samples.as<double>() : nullptr;
     launch_reduce_radiance(ra, c->stream);
     HIPCHK(c, hipGetLastError());
+    if (c->lay_on) {
+      // the same terms once more, summed per group, then the radiance reduction per layer plane
+      HIPCHK(c, c->s.prim_layers.ensure((size_t)GI_LAYER_COUNT * B.nprim * 24));
+      double *pl = c->s.prim_layers.as<double>();
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      if (c->lay_time) {
+        HIPCHK(c, hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) {
+          hipEventDestroy(e0);
+          return fail(c, GI_ERR_HIP, "layers: hipEventCreate failed");
+        }
+        (void)hipEventRecord(e0, c->stream);
+      }
+      launch_reduce_layers(a, pl, c->stream);
+      hipError_t le = hipGetLastError();
+      if (c->lay_time) {
+        (void)hipEventRecord(e1, c->stream);
+        float ms = 0.f;
+        if (le == hipSuccess) le = hipEventSynchronize(e1);
+        if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+        c->lay_ms += ms;
+        hipEventDestroy(e0);
+        hipEventDestroy(e1);
+      }
+      HIPCHK(c, le);
+      for (int l = 0; l < GI_LAYER_COUNT; l++) {
+        ra.prim_rgb = pl + (size_t)l * 3 * B.nprim;
+        ra.frame = c->s.lay_frame.as<double>() + (size_t)l * c->lay_npix * 6;
+        ra.samples = c->rad_want_samples
+                         ? c->s.lay_samples.as<double>() + (size_t)l * c->lay_npix * (size_t)ra.S * 3
+                         : nullptr;
+        launch_reduce_radiance(ra, c->stream);
+        HIPCHK(c, hipGetLastError());
+      }
+    }
   }
   return GI_OK;
 }

@@ -433,6 +433,9 @@ hipError_t launch_fb_compact(const uint32_t *list, uint32_t *count, int64_t chun
                              void *tmp, size_t &tmp_bytes, uint32_t *dense, uint32_t *total,
                              hipStream_t st);  // slot0 + indirect + Monte Carlo
 void launch_reduce(const RenderArgs &a, hipStream_t st);
+// reduce_prim_layers_kernel: the per-primary sums of the reduction's five groups (gi.h GI_LAYER_*),
+// layers = [GI_LAYER_COUNT][3 * nprim]; after launch_reduce, on its inputs
+void launch_reduce_layers(const RenderArgs &a, double *layers, hipStream_t st);
 void launch_owner_table(const uint32_t *off, int64_t n, uint32_t *tab, hipStream_t st);
 void launch_ind_tiles(const uint32_t *nind, int64_t nprim, uint32_t *rows, hipStream_t st);
 void launch_ind_row_tile(const uint32_t *rows, int64_t ntiles, uint64_t *tab, hipStream_t st);

@@ -13,6 +13,7 @@
 // so deferring the estimates into a query list changes only the fp summation order.
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "gi.h"  // GI_LAYER_*
 #include "gi_device.h"
 #include "gi_kernels.h"
 #include "gi_estimate.h"
@@ -1412,6 +1413,106 @@ __global__ __launch_bounds__(256) void reduce_prim_kernel(RenderArgs a) {
   }
 }
 
+// Light-path layers (gi.h GI_LAYER_*; DESIGN.md "Light-path layers"): reduce_prim_kernel's
+// traversal once more, every term read once and added to the sum of its group instead of the one
+// sum: the same mapping (a wave is a tile), the same order inside a group, the same entries
+// skipped, RB loads issued before their additions. layers: [GI_LAYER_COUNT][3 * nprim].
+// A kernel of its own: reduce_prim_kernel's text, and so its code, stays the one that was measured.
+__global__ __launch_bounds__(256) void reduce_prim_layers_kernel(RenderArgs a, double *layers) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t T = b >> 6;  // wave-uniform: blocks of whole waves
+  if (T * 64 >= a.nprim) return;
+  const bool own = b < a.nprim;
+  const int lane = (int)(b & 63);
+  const int64_t r0 = (int64_t)a.ind_rows[T];
+  const int M = (int)((int64_t)a.ind_rows[T + 1] - r0);
+  constexpr int RB = REDUCE_RB;
+  double s[3 * GI_LAYER_COUNT];
+#pragma unroll
+  for (int i = 0; i < 3 * GI_LAYER_COUNT; i++) s[i] = 0;
+  double *const surf = s + 3 * GI_LAYER_SURFACE, *const spec = s + 3 * GI_LAYER_SPECULAR;
+  double *const ind = s + 3 * GI_LAYER_INDIRECT;
+  const double *bs = a.base;
+  if (own) {
+    const uint32_t g0 = a.path_off[b], p1 = a.path_off[b + 1];
+    if (g0 < p1) {  // slot 0: the primary's own base
+      surf[0] += bs[3 * (int64_t)g0];
+      surf[1] += bs[3 * (int64_t)g0 + 1];
+      surf[2] += bs[3 * (int64_t)g0 + 2];
+    }
+    for (uint32_t g1 = g0 + 1; g1 < p1; g1 += RB) {  // its Monte Carlo paths' bases
+      double v[3 * RB];
+#pragma unroll
+      for (int u = 0; u < RB; u++) {
+        const int64_t g = g1 + u < p1 ? (int64_t)g1 + u : (int64_t)g1;
+        v[3 * u] = bs[3 * g];
+        v[3 * u + 1] = bs[3 * g + 1];
+        v[3 * u + 2] = bs[3 * g + 2];
+      }
+#pragma unroll
+      for (int u = 0; u < RB; u++)
+        if (g1 + u < p1) {
+          spec[0] += v[3 * u];
+          spec[1] += v[3 * u + 1];
+          spec[2] += v[3 * u + 2];
+        }
+    }
+  }
+  tiled_row_sum(a.ind_bmask, bs + 3 * a.ind_g0, r0, M, lane, ind[0], ind[1], ind[2]);
+  for (int l = 0; l < 2; l++) {
+    if (!a.qout[l]) continue;
+    const uint64_t *qk = a.qkey[l];
+    const double *qo = a.qout[l];
+    if (own) {
+      // the primary's own query (slot b): GLOBAL from the global list, CAUSTIC from the caustic
+      double *const q = s + 3 * (l == 0 ? GI_LAYER_GLOBAL : GI_LAYER_CAUSTIC);
+      if (qk[b] != ~0ull) {
+        q[0] += qo[3 * b];
+        q[1] += qo[3 * b + 1];
+        q[2] += qo[3 * b + 2];
+      }
+      const uint32_t q0 = a.qseg[l][b], q1 = a.qseg[l][b + 1];
+      const uint32_t *ss = a.sslot[l];
+      const int64_t qa = (int64_t)a.qapp[l];
+      for (uint32_t qb = q0; qb < q1; qb += RB) {  // its Monte Carlo paths' appends
+        int64_t sl[RB];
+        bool on[RB];
+        double v[3 * RB];
+#pragma unroll
+        for (int u = 0; u < RB; u++) sl[u] = qa + ss[qb + u < q1 ? qb + u : qb];
+#pragma unroll
+        for (int u = 0; u < RB; u++) on[u] = qb + u < q1 && qk[sl[u]] != ~0ull;
+#pragma unroll
+        for (int u = 0; u < RB; u++) {
+          v[3 * u] = v[3 * u + 1] = v[3 * u + 2] = 0.0;
+          if (on[u]) {
+            v[3 * u] = qo[3 * sl[u]];
+            v[3 * u + 1] = qo[3 * sl[u] + 1];
+            v[3 * u + 2] = qo[3 * sl[u] + 2];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; u++)
+          if (on[u]) {
+            spec[0] += v[3 * u];
+            spec[1] += v[3 * u + 1];
+            spec[2] += v[3 * u + 2];
+          }
+      }
+    }
+    if (l == 0) tiled_row_sum(a.ind_qmask, qo + 3 * a.qind_base, r0, M, lane, ind[0], ind[1], ind[2]);
+  }
+  if (own) {
+#pragma unroll
+    for (int k = 0; k < GI_LAYER_COUNT; k++) {
+      double *o = layers + 3 * ((int64_t)k * a.nprim + b);
+      o[0] = s[3 * k];
+      o[1] = s[3 * k + 1];
+      o[2] = s[3 * k + 2];
+    }
+  }
+}
+
 // Pass 2, one thread per output pixel
 __global__ __launch_bounds__(64) void reduce_kernel(RenderArgs a) {
   int pix = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1950,6 +2051,9 @@ void launch_owner_table(const uint32_t *off, int64_t n, uint32_t *tab, hipStream
 void launch_reduce(const RenderArgs &a, hipStream_t st) {
   reduce_prim_kernel<<<nblk((a.nprim + 63) & ~(int64_t)63, 256), 256, 0, st>>>(a);
   reduce_kernel<<<nblk(a.npix, 64), 64, 0, st>>>(a);
+}
+void launch_reduce_layers(const RenderArgs &a, double *layers, hipStream_t st) {
+  reduce_prim_layers_kernel<<<nblk((a.nprim + 63) & ~(int64_t)63, 256), 256, 0, st>>>(a, layers);
 }
 void launch_photons(const PhotonArgs &a, int mode, hipStream_t st) {
   if (a.n == 0) return;

@@ -23,6 +23,8 @@ Names follow the reference (ReillyBova/Global-Illumination, src/):
                    radiance frames with their variance, accumulation over passes and the tone
                    map (no reference counterpart; gi.h "radiance frames, accumulation over
                    passes, tone map")
+  render_layers / render_rays_layers / accum_add_*_layers: the same frames and passes split
+                   into light-path layers (gi.h "light-path layers")
   EstimateRadiance utils/photon_utils.cpp:72-162      (batched test seam)
   FindClosestQuick R3Shapes/R3Kdtree.cpp:688-848      (batched test seam)
   Intersects       R3Graphics/R3Scene.cpp:471-479     (batched test seam)
@@ -41,6 +43,11 @@ LIB_PATH = os.environ.get("GI_AMD_LIB") or os.path.join(_HERE, "libgi_amd.so")  
 GI_OK, GI_ERR_ARG, GI_ERR_IO, GI_ERR_HIP, GI_ERR_STATE, GI_ERR_UNSUPPORTED, GI_ERR_ALLOC = range(7)
 DISK, CONE, GAUSS = 0, 1, 2
 GLOBAL, CAUSTIC = 0, 1
+# light-path layers (gi.h GI_LAYER_*): plane l of render_layers' outputs, entry l of a layered
+# pass's context list; plane LAYER_TOTAL is the undivided frame
+LAYER_NAMES = ("surface", "specular", "indirect", "global", "caustic")
+LAYER_SURFACE, LAYER_SPECULAR, LAYER_INDIRECT, LAYER_GLOBAL, LAYER_CAUSTIC = range(5)
+LAYER_COUNT = LAYER_TOTAL = 5
 
 EXPORTED = [
     "gi_params_default", "gi_parse_args", "gi_create", "gi_create_devices", "gi_device_info",
@@ -53,6 +60,8 @@ EXPORTED = [
     "gi_denoise",
     "gi_render_radiance", "gi_render_rays_radiance", "gi_accum_reset", "gi_accum_add_image",
     "gi_accum_add_rays", "gi_accum_get", "gi_tonemap", "gi_radiance_bench",
+    "gi_render_layers", "gi_render_rays_layers", "gi_accum_add_image_layers",
+    "gi_accum_add_rays_layers", "gi_layers_timing",
     "gi_accum_get_counts", "gi_adaptive_params_default", "gi_accum_select", "gi_accum_add_tiles",
     "gi_accum_add_adaptive", "gi_adaptive_bench",
     "gi_vdenoise_params_default", "gi_denoise_radiance", "gi_accum_denoise",
@@ -261,6 +270,12 @@ def lib():
         L.gi_render_rays_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               P(RenderStats)]
+        L.gi_render_layers.argtypes = L.gi_render_radiance.argtypes
+        L.gi_render_rays_layers.argtypes = L.gi_render_rays_radiance.argtypes
+        L.gi_accum_add_image_layers.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(RenderStats)]
+        L.gi_accum_add_rays_layers.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               P(C.c_void_p), P(RenderStats)]
+        L.gi_layers_timing.argtypes = [C.c_void_p, C.c_int, P(C.c_double)]
         L.gi_accum_reset.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.gi_accum_add_image.argtypes = [C.c_void_p, C.c_int, P(RenderStats)]
         L.gi_accum_add_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -642,6 +657,78 @@ class Renderer:
             smp.ctypes.data if want_samples else None, C.byref(st)))
         stats = _stats_dict(st)
         return (mean, var, smp, stats) if want_samples else (mean, var, stats)
+
+    def render_layers(self, aa, width, height, want_samples=False):
+        """render_radiance with LAYER_COUNT + 1 planes per output (gi_render_layers): mean and
+        variance [6, H, W, 3] float32, samples [6, H, W, 4^aa, 3] float64; plane l < LAYER_COUNT
+        is light-path layer l (LAYER_NAMES), plane LAYER_TOTAL what render_radiance returns."""
+        S = 4 ** aa if 0 <= aa <= 15 else 1
+        n = LAYER_COUNT + 1
+        mean = np.zeros((n, height, width, 3), dtype=np.float32)
+        var = np.zeros((n, height, width, 3), dtype=np.float32)
+        smp = np.zeros((n, height, width, S, 3), dtype=np.float64) if want_samples else None
+        st = RenderStats()
+        self._check(lib().gi_render_layers(self._ctx, aa, width, height, mean.ctypes.data,
+                                           var.ctypes.data,
+                                           smp.ctypes.data if want_samples else None, C.byref(st)))
+        stats = _stats_dict(st)
+        return (mean, var, smp, stats) if want_samples else (mean, var, stats)
+
+    def render_rays_layers(self, width, height, spp, rays, ids=None, want_samples=False):
+        """render_rays_radiance with LAYER_COUNT + 1 planes per output (gi_render_rays_layers);
+        returns like render_layers, samples [6, H, W, spp, 3]."""
+        rays, ids = self._ray_batch(width, height, spp, rays, ids)
+        n = LAYER_COUNT + 1
+        mean = np.zeros((n, height, width, 3), dtype=np.float32)
+        var = np.zeros((n, height, width, 3), dtype=np.float32)
+        smp = (np.zeros((n, height, width, max(spp, 1), 3), dtype=np.float64) if want_samples
+               else None)
+        st = RenderStats()
+        self._check(lib().gi_render_rays_layers(
+            self._ctx, width, height, spp, rays.ctypes.data,
+            None if ids is None else ids.ctypes.data, mean.ctypes.data, var.ctypes.data,
+            smp.ctypes.data if want_samples else None, C.byref(st)))
+        stats = _stats_dict(st)
+        return (mean, var, smp, stats) if want_samples else (mean, var, stats)
+
+    @staticmethod
+    def _layer_list(layers):
+        """The C array of a layered pass: LAYER_COUNT Renderers (on this device, accumulators of
+        this one's size), None dropping a layer."""
+        layers = list(layers)
+        if len(layers) != LAYER_COUNT:
+            raise ValueError(f"{LAYER_COUNT} layer contexts (or None) expected, got {len(layers)}")
+        return (C.c_void_p * LAYER_COUNT)(*[None if r is None else r._ctx for r in layers])
+
+    def accum_add_image_layers(self, aa, layers):
+        """accum_add_image that also folds light-path layer l of the pass into the accumulator of
+        layers[l] (gi_accum_add_image_layers). Returns the pass's stats."""
+        st = RenderStats()
+        self._check(lib().gi_accum_add_image_layers(self._ctx, aa, self._layer_list(layers),
+                                                    C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_add_rays_layers(self, spp, rays, layers, ids=None):
+        """accum_add_rays with the layers folded as in accum_add_image_layers
+        (gi_accum_add_rays_layers)."""
+        w, h = getattr(self, "_accum_size", (0, 0))
+        if w:
+            rays, ids = self._ray_batch(w, h, spp, rays, ids)
+        else:  # no reset yet: the library reports it
+            rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+            ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        st = RenderStats()
+        self._check(lib().gi_accum_add_rays_layers(self._ctx, spp, rays.ctypes.data,
+                                                   None if ids is None else ids.ctypes.data,
+                                                   self._layer_list(layers), C.byref(st)))
+        return _stats_dict(st)
+
+    def layers_timing(self, on):
+        """Switch the HIP-event timing of the layer reduction's kernel on or off
+        (gi_layers_timing); returns the ms summed since it was last switched on."""
+        ms = C.c_double(0.0)
+        self._check(lib().gi_layers_timing(self._ctx, int(bool(on)), C.byref(ms)))
+        return ms.value
 
     def accum_reset(self, width, height):
         """Size and empty the context's accumulator over passes (gi_accum_reset)."""

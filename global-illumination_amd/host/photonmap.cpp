@@ -43,6 +43,16 @@
 // estimates whose radii shrink from -gd / -cd by the schedule of gi_progressive_radius. Refused
 // before a device is opened with -adaptive, -views, -cache or -gpus N. The accumulator file does
 // not record the flag: a resumed run must be given the same -progressive A.
+// Extension: -layers PREFIX: the frame's light-path layers (gi.h GI_LAYER_*) as float means in
+// PREFIX_surface.pfm, _specular, _indirect, _global and _caustic. Without a radiance flag the
+// frame is rendered once more by gi_render_layers for them; with one, every pass is a layered one
+// (gi_accum_add_image_layers) over five scene-less contexts. The usual image and -radiance come
+// from the total and do not change. With -vdenoise L the surface, indirect, global and caustic
+// layers are each filtered under their own variance (gi_accum_denoise of the layer's context, the
+// frame's planes), the specular layer is left as it is, and the written image is gi_tonemap of
+// their sum (per channel the five floats widened to double, added in layer order, rounded once):
+// what a mirror or glass shows is not filtered by the planes of the surface that shows it.
+// Refused (exit 1) with -adaptive, -views, -progressive, -save_accum, -load_accum or -gpus N.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -319,6 +329,28 @@ static bool ReadViews(const char *path, std::vector<gi_camera> &views, int &bad_
   return true;
 }
 
+static const char *const LAYER_SUFFIX[GI_LAYER_COUNT] = {"_surface.pfm", "_specular.pfm", "_indirect.pfm",
+                                                        "_global.pfm", "_caustic.pfm"};
+// -layers with passes: one scene-less context per layer, destroyed with the object
+struct LayerContexts {
+  gi_ctx *c[GI_LAYER_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~LayerContexts() {
+    for (gi_ctx *x : c)
+      if (x) gi_destroy(x);
+  }
+};
+// plane l of means (GI_LAYER_COUNT planes of w * h * 3 floats) to PREFIX + its suffix
+static bool WriteLayers(const char *prefix, int w, int h, const std::vector<float> &means) {
+  for (int l = 0; l < GI_LAYER_COUNT; l++) {
+    const std::string path = std::string(prefix) + LAYER_SUFFIX[l];
+    if (gi_write_image_float(path.c_str(), w, h, means.data() + (size_t)l * w * h * 3) != GI_OK) {
+      fprintf(stderr, "Unable to write image %s\n", path.c_str());
+      return false;
+    }
+  }
+  return true;
+}
+
 // path with ".%04d" of k before its extension (appended when it has none)
 static std::string NumberedPath(const char *path, int k) {
   std::string p(path);
@@ -353,6 +385,11 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (vdenoise_levels) rad.any = true;
+  const char *layers_prefix = nullptr;
+  if (!TakeValue(argc, argv, "-layers", &layers_prefix)) {
+    fprintf(stderr, "Invalid program argument: -layers");
+    return 1;
+  }
   // -views FILE / -history H: one of the radiance flags; malformed ones exit -1
   const char *views_file = nullptr, *history_text = nullptr;
   std::vector<gi_camera> views;
@@ -364,6 +401,11 @@ int main(int argc, char **argv) {
   if (!TakeValue(argc, argv, "-history", &history_text)) {
     fprintf(stderr, "Invalid program argument: -history\n");
     return -1;
+  }
+  if (layers_prefix && (rad.adaptive_tile || views_file || rad.progressive || rad.save_accum || rad.load_accum)) {
+    fprintf(stderr, "-layers takes whole-frame passes of one view: not with -adaptive, -views, -progressive, "
+                    "-save_accum or -load_accum\n");
+    return 1;
   }
   if (history_text) {
     char *end = nullptr;
@@ -430,6 +472,10 @@ int main(int argc, char **argv) {
     }
     if (ds.count == 0) ds.count = 1;
   }
+  if (layers_prefix && ds.count > 1) {
+    fprintf(stderr, "-layers renders on one device: not with -gpus %d\n", ds.count);
+    return 1;
+  }
   if (rad.progressive && P.irradiance_cache) {
     fprintf(stderr, "Invalid program argument: -progressive (not with -cache)\n");
     return -1;
@@ -456,6 +502,15 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Unable to initialise %d HIP device(s) starting at %d\n", ds.count, ds.devices[0]);
     return -1;
   }
+  LayerContexts lay;
+  std::vector<float> layer_means(layers_prefix ? (size_t)(GI_LAYER_COUNT + 1) * w * h * 3 : 0);
+  if (layers_prefix && rad.any)
+    for (int l = 0; l < GI_LAYER_COUNT; l++)
+      if (gi_create(&lay.c[l], ds.devices[0]) != GI_OK) {
+        fprintf(stderr, "Unable to initialise HIP device %d\n", ds.devices[0]);
+        gi_destroy(ctx);
+        return -1;
+      }
   gi_set_params(ctx, &P);
   ProgressState prog = {P.verbose != 0, {-1, -1, -1}};
   gi_set_progress(ctx, OnProgress, &prog);
@@ -551,6 +606,7 @@ int main(int argc, char **argv) {
         ok = gi_accum_import(ctx, w, h, loaded.state.data(), loaded.counts.data()) == GI_OK &&
              gi_accum_get(ctx, nullptr, nullptr, &least, nullptr) == GI_OK;
       else if (ok && !carried) ok = gi_accum_reset(ctx, w, h) == GI_OK;
+      for (int l = 0; ok && layers_prefix && l < GI_LAYER_COUNT; l++) ok = gi_accum_reset(lay.c[l], w, h) == GI_OK;
       gi_adaptive_params ap;
       gi_adaptive_params_default(&ap);
       ap.tile_px = rad.adaptive_tile ? rad.adaptive_tile : ap.tile_px;
@@ -588,7 +644,7 @@ int main(int argc, char **argv) {
           if (ok && active == 0) break;  // every tile is at the threshold: nothing was rendered
           primary_samples += (long long)active << (2 * aa);
         } else if (ok) {
-          ok = gi_accum_add_image(ctx, aa, &ps) == GI_OK;
+          ok = (layers_prefix ? gi_accum_add_image_layers(ctx, aa, lay.c, &ps) : gi_accum_add_image(ctx, aa, &ps)) == GI_OK;
           primary_samples += ((long long)w * h) << (2 * aa);
         }
         }
@@ -639,9 +695,25 @@ int main(int argc, char **argv) {
         gi_vdenoise_params_default(&vp);
         vp.levels = vdenoise_levels;
         filtered.resize((size_t)w * h * 3);
-        ok = ok && gi_accum_denoise(ctx, history ? cur_feat.data() : feat.data(), &vp, filtered.data(), nullptr,
-                                    &vdenoise_ms) == GI_OK;
+        if (!layers_prefix)
+          ok = ok && gi_accum_denoise(ctx, history ? cur_feat.data() : feat.data(), &vp, filtered.data(), nullptr,
+                                      &vdenoise_ms) == GI_OK;
+        // -layers: every layer but the specular one filtered under its own variance, then their sum
+        std::vector<double> sum(layers_prefix ? filtered.size() : 0, 0.0);
+        std::vector<float> part(sum.size());
+        for (int l = 0; ok && layers_prefix && l < GI_LAYER_COUNT; l++) {
+          double ms = 0.0;
+          // (a failure's message is the layer context's)
+          if (l == GI_LAYER_SPECULAR) ok = gi_accum_get(lay.c[l], part.data(), nullptr, nullptr, nullptr) == GI_OK;
+          else ok = gi_accum_denoise(lay.c[l], feat.data(), &vp, part.data(), nullptr, &ms) == GI_OK;
+          if (!ok) fprintf(stderr, "%s\n", gi_last_error(lay.c[l]));
+          vdenoise_ms += ms;
+          for (size_t i = 0; i < sum.size(); i++) sum[i] += (double)part[i];
+        }
+        for (size_t i = 0; i < sum.size(); i++) filtered[i] = (float)sum[i];
       }
+      for (int l = 0; ok && layers_prefix && l < GI_LAYER_COUNT; l++)
+        ok = gi_accum_get(lay.c[l], layer_means.data() + (size_t)l * w * h * 3, nullptr, nullptr, nullptr) == GI_OK;
       ok = ok && gi_tonemap(ctx, w, h, vdenoise_levels ? filtered.data() : mean.data(), rad.exposure,
                             rad.white, rgbf.data(), rgb.data()) == GI_OK;
       acc_n = n;
@@ -656,6 +728,13 @@ int main(int argc, char **argv) {
         return -1;
       }
     } else if (gi_render_image(ctx, aa, w, h, rgb.data(), denoise_levels ? rgbf.data() : nullptr, &rs) != GI_OK) {
+      fprintf(stderr, "%s\n", gi_last_error(ctx));
+      gi_destroy(ctx);
+      return -1;
+    }
+    // -layers without passes: the frame once more, split (the image above is gi_render_image's own)
+    if (layers_prefix && !rad.any &&
+        gi_render_layers(ctx, aa, w, h, layer_means.data(), nullptr, nullptr, nullptr) != GI_OK) {
       fprintf(stderr, "%s\n", gi_last_error(ctx));
       gi_destroy(ctx);
       return -1;
@@ -718,6 +797,7 @@ int main(int argc, char **argv) {
       if (k < nviews - 1) gi_destroy(ctx);
       return -1;
     }
+    if (layers_prefix && !WriteLayers(layers_prefix, w, h, layer_means)) return -1;
     if (P.verbose) {
       printf("Wrote image to %s ...\n", out_k.c_str());
       printf("  Time = %.2f seconds\n",

@@ -387,6 +387,60 @@ int gi_accum_get(gi_ctx *ctx, float *mean, float *variance, int64_t *nsamples, d
 /* counts: W*H int64, rows from the bottom (optional); *total = sum of n_p (optional) */
 int gi_accum_get_counts(gi_ctx *ctx, int64_t *counts, int64_t *total);
 
+/* ---- light-path layers of radiance frames and passes --------------------------------------- */
+/* A primary sample's radiance is the sequential fp64 sum of its path bases and photon-map
+ * estimates (DESIGN.md "Light-path layers"). These calls return that sum split into the five
+ * groups the reduction visits, each a sequential fp64 sum from +0 in the reduction's own order,
+ * with the entries it skips (empty query slots, indirect paths without a stored base) skipped:
+ *   SURFACE   the primary's own base: ambient, emission and direct light at the primary hit, or
+ *             the background on a miss;
+ *   SPECULAR  the bases of its transmissive and specular sample paths (Monte Carlo paths), then
+ *             their appended queries of the global list, then those of the caustic list:
+ *             everything that reaches the pixel through a Monte Carlo path, those paths' indirect
+ *             sub-paths and caustic queries included (what a mirror or glass shows);
+ *   INDIRECT  the bases of its indirect sample paths, then their global-map queries;
+ *   GLOBAL    the primary's own global-map query (-photon_viz, -fast_global; else zero);
+ *   CAUSTIC   the primary's own caustic-map query.
+ * A layer's sample is formed like a radiance sample (the sum over the dof_test lens primaries,
+ * then / dof_test), and its m, M2, mean and variance are gi_render_radiance's definitions applied
+ * to that layer's samples. Plane GI_LAYER_TOTAL is gi_render_radiance's own output, bit for bit.
+ * The layers of a sample add up to the total only up to the rounding of two summation orders
+ * (relative 2 (n - 1) 2^-53 for n non-negative terms). A layer's variance is that layer's own: the
+ * layers of one sample are correlated, so the variances do not add up to the total's.
+ * No reference counterpart. */
+enum { GI_LAYER_SURFACE = 0, GI_LAYER_SPECULAR = 1, GI_LAYER_INDIRECT = 2,
+       GI_LAYER_GLOBAL = 3, GI_LAYER_CAUSTIC = 4, GI_LAYER_COUNT = 5,
+       GI_LAYER_TOTAL = 5 /* plane index of the undivided frame */ };
+/* gi_render_radiance / gi_render_rays_radiance with GI_LAYER_COUNT + 1 planes per output,
+ * layer-major: mean, variance 6*W*H*3 floats, samples 6*W*H*S*3 doubles, each plane laid out as
+ * there. Any of the three may be NULL, not all. Counters, batches, argument checks and errors are
+ * those calls'. */
+int gi_render_layers(gi_ctx *ctx, int aa, int width, int height, float *mean, float *variance,
+                     double *samples, gi_render_stats *stats);
+int gi_render_rays_layers(gi_ctx *ctx, int width, int height, int spp, const gi_ray *rays,
+                          const uint64_t *ids /* may be NULL */, float *mean, float *variance,
+                          double *samples, gi_render_stats *stats);
+/* One pass. The total is folded into ctx's accumulator exactly as gi_accum_add_image /
+ * gi_accum_add_rays do; layer l's (S, m_l, M2_l) is folded by the same update into the
+ * accumulator of layers[l] (a NULL entry drops that layer), so gi_accum_get, gi_accum_denoise,
+ * gi_accum_export and gi_accum_merge* serve a layer like any accumulator. A layer context is a
+ * one-device context on ctx's device whose accumulator (gi_accum_reset / gi_accum_import; it
+ * needs no scene) has the size of ctx's; it is not ctx and is listed once. GI_ERR_UNSUPPORTED when
+ * ctx is a device set, GI_ERR_STATE when ctx or a layer context has no accumulator, GI_ERR_ARG
+ * for a null `layers` or any other layer context, all before anything is rendered: a refused call
+ * changes nothing. Otherwise as gi_accum_add_image / gi_accum_add_rays.
+ * Accepted limits: whole-frame passes only (no layered gi_accum_add_tiles, adaptive or
+ * progressive passes); gi_accum_reproject knows nothing of layers (a caller may reproject the
+ * contexts of the diffuse layers and reset the SPECULAR one). */
+int gi_accum_add_image_layers(gi_ctx *ctx, int aa, gi_ctx *const layers[GI_LAYER_COUNT],
+                              gi_render_stats *stats);
+int gi_accum_add_rays_layers(gi_ctx *ctx, int spp, const gi_ray *rays, const uint64_t *ids,
+                             gi_ctx *const layers[GI_LAYER_COUNT], gi_render_stats *stats);
+/* Diagnostics: the summed HIP-event time of the layer reduction's kernel alone. on != 0 zeroes
+ * the sum and makes every later layered render time the kernel (one event pair and one wait per
+ * batch); on == 0 stops. *ms (optional) receives the sum so far, before it is zeroed. */
+int gi_layers_timing(gi_ctx *ctx, int on, double *ms);
+
 /* ---- accumulator state: export, import and merge ------------------------------------------ */
 /* The state of a W x H accumulator (DESIGN.md "Accumulator state"), the device's own bits with no
  * rounding:
