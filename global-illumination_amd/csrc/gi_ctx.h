@@ -25,7 +25,8 @@ namespace gi_internal {
 using namespace gi;
 
 // photon map on the host: the photons and, when built here (gi_photons.cpp kd_build), the
-// implicit complete kd tree over them (leaf l holds photons [l*n/L, (l+1)*n/L))
+// implicit complete kd tree over them (leaf l holds photons [start(l), start(l + 1)),
+// gi_layout.h kd_leaf_start; nleaves == 1 << levels, check_kd_shape)
 struct HostMap {
   std::vector<gi_photon> storage;  // emission order
   std::vector<int32_t> perm;       // kd order -> storage index
@@ -310,6 +311,14 @@ inline void set_err(gi_ctx *c, const std::string &msg) {
 inline int fail(gi_ctx *c, int code, const std::string &msg) {
   set_err(c, msg);
   return code;
+}
+
+// nleaves == 1 << levels (gi_layout.h kd_levels_ok): the leaf ranges are computed by a shift, so
+// a map whose shape breaks it is refused where it is made, exported or handed to a kernel
+inline int check_kd_shape(gi_ctx *c, int nleaves, int levels) {
+  if (kd_levels_ok(nleaves, levels)) return GI_OK;
+  return fail(c, GI_ERR_STATE, "photon map: " + std::to_string(nleaves) + " kd leaves are not 2^" +
+                                 std::to_string(levels));
 }
 
 #define HIPCHK(ctx, call)                                                                   \

@@ -84,6 +84,7 @@ int ensure_dk(gi_ctx *c, KnnArgs &k) {
   MapScratch &XS = c->s.map[map_index(k)];
   DevMap &D = c->res.dmap[map_index(k)];
   if (!c->use_dk || D.n == 0 || k.K <= 0) return GI_OK;
+  if (int rc = check_kd_shape(c, k.map.nleaves, k.map.levels)) return rc;
   if (D.dk_k != k.K || D.dk_r2 != k.r2f) {
     D.dk_k = -1;
     HIPCHK(c, XS.dk_q.ensure((size_t)D.n * 16));
@@ -264,6 +265,7 @@ int run_knn(gi_ctx *c, KnnArgs k, int64_t nq, double *ms) {
   MapExec &X = c->mx[map_index(k)];
   MapScratch &XS = c->s.map[map_index(k)];
   const hipStream_t st = X.st;
+  if (int rc = check_kd_shape(c, k.map.nleaves, k.map.levels)) return rc;
   const int kind = knn_kind(c, k);
   if (k.mode != KNN_MODE_DK) c->last_kind[map_index(k)] = kind;
   if (kind == 10) {

@@ -361,7 +361,8 @@ void knn_wave_kernel(KnnArgs a) {
             const int li = __ffsll((long long)__ballot(cb == mn)) - 1;
             lm &= ~(1ull << li);
             const int leaf = lf0 + li - L;
-            int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+            int64_t s0, s1;
+            kd_leaf_range(a.map, leaf, s0, s1);
             if (need_dk) {
               need_dk = false;
               double best = INFINITY;
@@ -450,7 +451,8 @@ void knn_wave_kernel(KnnArgs a) {
           node = 2 * node + ((qa - nd.lo.w >= 0.0f) ? 1 : 0);
         }
         int leaf = node - L;
-        int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+        int64_t s0, s1;
+        kd_leaf_range(a.map, leaf, s0, s1);
         double best = INFINITY;
         for (int64_t b = s0; b < s1; b += 64) {
           int64_t ii = b + lane;
@@ -508,7 +510,8 @@ void knn_wave_kernel(KnnArgs a) {
             }
           } else {
             int leaf = node - L;
-            int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+            int64_t s0, s1;
+            kd_leaf_range(a.map, leaf, s0, s1);
             visited += (uint32_t)(s1 - s0);
             if (prof) { uint64_t n = clock64(); pc[0] += n - pt; pt = n; }
             // the leaf's photons, LB batches of 64 loaded before any is used: one memory round
@@ -725,8 +728,7 @@ __global__ __launch_bounds__(64) void knn_lane_kernel(KnnArgs a) {
     }
     int64_t s0 = 0, s1 = 0;
     if (leaf >= 0) {
-      s0 = ((int64_t)leaf * N) / L;
-      s1 = ((int64_t)(leaf + 1) * N) / L;
+      kd_leaf_range(a.map, leaf, s0, s1);
       visited += (uint32_t)(s1 - s0);
     }
     // converged leaf loop: CH photon loads in flight per lane

@@ -193,7 +193,8 @@ __device__ __forceinline__ bool exact_dk2(const KnnArgs &a, int lane, float cx, 
   uint32_t rd = walk_within(a.map.nodes, L, RA2, stk,
       [&](const KdNode &b) { return kd_box_d2(b.lo, b.hi, cx, cy, cz); },
       [&](int lf) {
-        int64_t a0 = ((int64_t)lf * N) / L, a1 = ((int64_t)(lf + 1) * N) / L;
+        int64_t a0, a1;
+        kd_leaf_range(a.map, lf, a0, a1);
         for (int64_t bb = a0; bb < a1; bb += 64) {
           int64_t ii = bb + lane;
           bool take = false;
@@ -294,7 +295,8 @@ __device__ __forceinline__ void chunk_bound_gather(const KnnArgs &a, int lane, b
     }
     cleaf = node;
     int leaf = node - L;
-    int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+    int64_t s0, s1;
+    kd_leaf_range(a.map, leaf, s0, s1);
     if (a.map.dk) {
       // d_K(c) <= |c - p| + d_K(p) for every photon p of c's leaf (per-photon bounds, KdView::dk)
       double best = INFINITY;
@@ -366,7 +368,8 @@ __device__ __forceinline__ void chunk_bound_gather(const KnnArgs &a, int lane, b
           return gap2(b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z, bl, bh);
         },
         [&](int leaf) {
-          int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+          int64_t s0, s1;
+          kd_leaf_range(a.map, leaf, s0, s1);
           for (int64_t b = s0; b < s1; b += 64) {
             int64_t ii = b + lane;
             bool take = false;

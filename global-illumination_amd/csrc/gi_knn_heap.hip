@@ -96,7 +96,8 @@ __device__ __forceinline__ int knn_search(const KdView &M, float qx, float qy, f
       live = kd_next(nodes, node, qx, qy, qz);
     }
     if (leaf < 0) break;
-    int64_t s0 = ((int64_t)leaf * M.n) / L, s1 = ((int64_t)(leaf + 1) * M.n) / L;
+    int64_t s0, s1;
+    kd_leaf_range(M, leaf, s0, s1);
     for (int64_t ii = s0; ii < s1; ii += 4) {
       float4 p[4];
 #pragma unroll
@@ -247,7 +248,8 @@ __global__ __launch_bounds__(64) void cached_kernel(KnnArgs a) {
             continue;
           }
           int leaf = node - L;
-          int64_t s0 = ((int64_t)leaf * a.map.n) / L, s1 = ((int64_t)(leaf + 1) * a.map.n) / L;
+          int64_t s0, s1;
+          kd_leaf_range(a.map, leaf, s0, s1);
           for (int64_t ii = s0; ii < s1; ii++) {
             float4 p = pos[ii];
             float d2 = photon_d2(qp.x, qp.y, qp.z, p.x, p.y, p.z);

@@ -132,7 +132,9 @@ struct DCamera {
 //   rgbe[i]   = packed RGBE bytes (r | g<<8 | b<<16 | e<<24)
 //   nodes[j]  = (split, bitcast(axis)) for internal node j in [1, nleaves) of the implicit
 //               complete tree; leaf l in [nleaves, 2*nleaves) holds photons
-//               [start(l - nleaves), start(l - nleaves + 1)), start(j) = j * n / nleaves.
+//               [start(l - nleaves), start(l - nleaves + 1)), start(j) = (j * n) >> levels
+//               (kd_leaf_start). nleaves == 1 << levels always (kd_levels_ok; both builders
+//               double from 1), so the shift is floor(j * n / nleaves) without a division.
 struct KdView {
   const float *pos4;       // float4
   const uint32_t *rgbe;
@@ -147,5 +149,26 @@ struct KdView {
   // within r; nullptr when not computed for this K / r
   const float *dk;
 };
+
+#ifdef __HIPCC__
+#define GI_LAYOUT_HD __host__ __device__ __forceinline__
+#else
+#define GI_LAYOUT_HD inline
+#endif
+
+// the invariant every holder of (nleaves, levels) keeps: checked where a map gets them
+GI_LAYOUT_HD bool kd_levels_ok(int32_t nleaves, int32_t levels) {
+  return levels >= 0 && levels < 31 && nleaves == (int32_t)1 << levels;
+}
+
+// start(j) of the layout above, j in [0, 2^levels]: the first photon of leaf j (n for j = 2^levels).
+// j, n >= 0, so the shift equals the truncating division by 2^levels; j * n < 2^62 for n < 2^31.
+GI_LAYOUT_HD int64_t kd_leaf_start(int64_t n, int levels, int64_t j) { return (j * n) >> levels; }
+
+// photons [s0, s1) of leaf `leaf` (0-based among the leaves)
+GI_LAYOUT_HD void kd_leaf_range(const KdView &m, int leaf, int64_t &s0, int64_t &s1) {
+  s0 = kd_leaf_start(m.n, m.levels, leaf);
+  s1 = kd_leaf_start(m.n, m.levels, (int64_t)leaf + 1);
+}
 
 }  // namespace gi

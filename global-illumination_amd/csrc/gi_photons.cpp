@@ -28,7 +28,8 @@ void rgbe_dec(const uint8_t *in, double c[3]) {
 
 // ---------------------------------------------------------------------------------------
 // photon map: host kd build of an implicit complete tree (leaf l holds photons
-// [l*n/L, (l+1)*n/L)); split = median of the node's range along its longest bbox axis.
+// [start(l), start(l + 1)), gi_layout.h kd_leaf_start); split = median of the node's range
+// along its longest bbox axis.
 // Any kd-tree gives the same k-NN set (up to ties at the k-th distance, broken here by
 // (d2, kd-order index)); the reference's tree is R3Kdtree.cpp:1552-1671.
 // ---------------------------------------------------------------------------------------
@@ -36,9 +37,9 @@ void kd_rec(HostMap &M, int node, int a, int b, int depth_par) {
   int64_t n = (int64_t)M.storage.size();
   int L = M.nleaves;
   if (node >= L) return;
-  int64_t lo = (int64_t)a * n / L, hi = (int64_t)b * n / L;
+  int64_t lo = kd_leaf_start(n, M.levels, a), hi = kd_leaf_start(n, M.levels, b);
   int midleaf = (a + b) / 2;
-  int64_t mid = (int64_t)midleaf * n / L;
+  int64_t mid = kd_leaf_start(n, M.levels, midleaf);
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
   for (int64_t i = lo; i < hi; i++) {
     const float *p = M.storage[M.perm[i]].pos;
@@ -103,7 +104,7 @@ void kd_build(HostMap &M, int leaf_size, int threads) {
     float *b = &M.nodes[8 * (size_t)(L + l)];
     b[0] = b[1] = b[2] = INFINITY;
     b[4] = b[5] = b[6] = -INFINITY;
-    int64_t s0 = (int64_t)l * n / L, s1 = (int64_t)(l + 1) * n / L;
+    int64_t s0 = kd_leaf_start(n, M.levels, l), s1 = kd_leaf_start(n, M.levels, l + 1);
     for (int64_t i = s0; i < s1; i++)
       for (int k = 0; k < 3; k++) {
         b[k] = std::min(b[k], M.pos4[4 * i + k]);
@@ -124,6 +125,7 @@ int upload_map(gi_ctx *c, int mi) {
   HostMap &H = c->hmap[mi];
   DevMap &D = c->res.dmap[mi];
   int64_t n = (int64_t)H.storage.size();
+  if (int rc = check_kd_shape(c, H.nleaves, H.levels)) return rc;
   HIPCHK(c, upload(D.pos4, H.pos4.data(), H.pos4.size() * 4, c->stream));
   HIPCHK(c, upload(D.rgbe, H.rgbe.data(), H.rgbe.size() * 4, c->stream));
   HIPCHK(c, upload(D.nodes, H.nodes.data(), H.nodes.size() * 4, c->stream));
@@ -159,6 +161,7 @@ int build_map_device(gi_ctx *c, int mi, bool upload_storage = true) {
                             reinterpret_cast<uint32_t *>(H.perm.data()), &H.nleaves, &H.levels,
                             c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = check_kd_shape(c, H.nleaves, H.levels)) return rc;
   D.n = n;
   D.nleaves = H.nleaves;
   D.levels = H.levels;
@@ -603,6 +606,7 @@ int gi_get_kd_tree(gi_ctx *c, int map, float *nodes, int64_t node_floats, int32_
   const HostMap &H = c->hmap[map];
   const DevMap &D = c->res.dmap[map];
   const int64_t nn = (int64_t)H.storage.size();
+  if (int rc = check_kd_shape(c, H.nleaves, H.levels)) return rc;
   if (n) *n = nn;
   if (nleaves) *nleaves = H.nleaves;
   const int64_t nf = (int64_t)16 * H.nleaves;

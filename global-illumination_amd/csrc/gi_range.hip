@@ -111,7 +111,8 @@ void knn_range_kernel(KnnArgs a) {
               return gap2(b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z, bl, bh);
             },
             [&](int leaf) {
-              int64_t s0 = ((int64_t)leaf * N) / L, s1 = ((int64_t)(leaf + 1) * N) / L;
+              int64_t s0, s1;
+              kd_leaf_range(a.map, leaf, s0, s1);
               for (int64_t b = s0; b < s1; b += 64) {
                 int64_t ii = b + lane;
                 bool take = false;
