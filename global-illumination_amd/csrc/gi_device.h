@@ -571,15 +571,31 @@ __device__ __forceinline__ int scene_intersect_b(const SceneView &S, V org, V di
   bool found = false;
   V hp = mk(0, 0, 0), hn = mk(0, 0, 0);
   int hnode = 0, hmat = -1, htri = -1;
+  int skip_to = 0;  // nodes below it lie under a node whose box this ray failed
   for (int ni = 0; ni < S.nnodes; ni++) {
     const DNode &nd = S.nodes[ni];
-    if (nd.elem_count == 0) continue;
+    if (ni < skip_to) continue;
     // local ray: apply the chain root -> node
     V lo = org, ldir = dir;
     double scale = 1.0;
     bool ok = true;
     for (int k = 0; k < nd.depth; k++) {
       const DNode &a = S.nodes[nd.chain[k]];
+      // the node's own box, in its parent's frame, before its transform (R3SceneNode.cpp:
+      // 438-442). Its ancestors' boxes were tested when the walk came to them: a failure there
+      // skipped this node. Without this test a ray that grazes a node's box (a corner or an
+      // edge of the scene's, say) takes hits that the reference never looks for.
+      if (k == nd.depth - 1 && !box_contains(a.bmin, a.bmax, lo)) {
+        double bt;
+        // (against a hit's t only, not a shadow ray's t_init: a ray that grazes the node's box
+        // can enter it, by the face R3Intersects(ray, box) reports, several 1e-6 after it meets
+        // a shape in it, and the reference, which searches unbounded, still takes that hit)
+        if (!ray_box(lo, ldir, a.bmin, a.bmax, &bt, nullptr) ||
+            isPos(bt - (found ? closest : kInf) / scale)) {
+          ok = false;
+          break;
+        }
+      }
       double lv;
       if (a.identity) {
         lv = len(ldir);
@@ -592,15 +608,24 @@ __device__ __forceinline__ int scene_intersect_b(const SceneView &S, V org, V di
       if (isNegOrZero(lv)) { ok = false; break; }
       if (!isZero(lv - 1.0)) scale *= lv;
     }
-    if (!ok) continue;
+    if (!ok) {  // the reference returns from the node: none of its subtree is visited
+      skip_to = nd.skip;
+      continue;
+    }
+    if (nd.elem_count == 0) continue;
     // the pretest's slab reciprocals only when it runs (a wave-uniform flag: hard-light scenes
     // skip three fp64 divisions per node and ray)
     const V linv = S.elem_pretest ? mk(1.0 / ldir.x, 1.0 / ldir.y, 1.0 / ldir.z) : mk(0, 0, 0);
+    // closest in this node's units: divided once on entry and then carried from element to
+    // element as R3SceneNode::Intersects carries its closest_t (R3SceneNode.cpp:457-471). Taking
+    // it back from the world value, (ec * scale) / scale, is ec only to an ulp under a scale
+    // that is no power of two, and an ulp above lets a later coplanar element take a tie that
+    // the reference gives to the earlier one.
+    double maxt = closest / scale;
     for (int ei = 0; ei < nd.elem_count; ei++) {
       const int gei = nd.elem_first + ei;
       if (gei < 64 && !((emask >> gei) & 1ull)) continue;
       const DElement &el = S.elems[gei];
-      double maxt = closest / scale;
       if (S.elem_pretest && !elem_maybe_hit(el, lo, linv, maxt)) continue;
       auto box_pass = [&]() -> bool {
         if (box_contains(el.bmin, el.bmax, lo)) return true;
@@ -631,6 +656,7 @@ __device__ __forceinline__ int scene_intersect_b(const SceneView &S, V org, V di
       if (shapes_first && !box_pass()) continue;
       found = true;
       closest = ec * scale;
+      maxt = ec;
       hp = ep;
       hn = en;
       hnode = ni;

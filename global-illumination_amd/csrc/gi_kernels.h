@@ -469,5 +469,13 @@ void launch_math_probe(int fn, int64_t n, const double *x, const double *y, doub
 void launch_intersect(const SceneView &S, int64_t n, const double *org, const double *dir,
                       int32_t *hit, double *t, double *point, double *normal, int32_t *mat,
                       hipStream_t st);
+// the probes of include/gi.h; false: `instance` is unknown or does not hold the scene's kinds
+bool launch_intersect_probe(const SceneView &S, int instance, int64_t n, const double *org,
+                            const double *dir, const int32_t *hint, int32_t *hit, double *t,
+                            double *point, double *normal, int32_t *mat, int32_t *tri,
+                            hipStream_t st);
+bool launch_illum_probe(const SceneView &S, int instance, int64_t n, const double *p_scene,
+                        const int32_t *light, const double *r12, const double *p_in, int use_mask,
+                        double *p_light, int32_t *lit, hipStream_t st);
 
 }  // namespace gi

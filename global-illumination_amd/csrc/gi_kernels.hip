@@ -1766,6 +1766,49 @@ __global__ void intersect_kernel(SceneView S, int64_t n, const double *org, cons
   mat[i] = ok ? h.mat : -2;
 }
 
+// gi_intersect_probe: the same cast through a chosen instance of the walk, with the ray's hint
+// triangle (hint == nullptr: none) and the triangle hit
+template <uint32_t KINDS>
+__global__ void intersect_probe_kernel(SceneView S, int64_t n, const double *org, const double *dir,
+                                       const int32_t *hint, int32_t *hit, double *t, double *point,
+                                       double *normal, int32_t *mat, int32_t *tri) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Hit h;
+  bool ok = scene_intersect<KINDS>(S, ld3(org + 3 * i), ld3(dir + 3 * i), h, hint ? hint[i] : -1);
+  hit[i] = ok;
+  t[i] = ok ? h.t : 0.0;
+  point[3 * i] = ok ? h.p.x : 0; point[3 * i + 1] = ok ? h.p.y : 0; point[3 * i + 2] = ok ? h.p.z : 0;
+  normal[3 * i] = ok ? h.n.x : 0; normal[3 * i + 1] = ok ? h.n.y : 0; normal[3 * i + 2] = ok ? h.n.z : 0;
+  mat[i] = ok ? h.mat : -2;
+  tri[i] = ok ? h.tri : -1;
+}
+
+// gi_illum_probe: illum_test as soft_light calls it. light[i] >= 0 (the host has checked that it
+// is an area or rect light): the sample point of coefficients (r1, r2), light_sample_point's
+// expression, and with use_mask soft_light's occluder mask; light[i] < 0: the caller's point.
+template <uint32_t KINDS>
+__global__ void illum_probe_kernel(SceneView S, int64_t n, const double *p_scene,
+                                   const int32_t *light, const double *r12, const double *p_in,
+                                   int use_mask, double *p_light, int32_t *lit) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V p = ld3(p_scene + 3 * i);
+  V sp;
+  uint64_t em = ~0ull;
+  if (light[i] >= 0) {
+    const DLight &L = S.lights[light[i]];
+    const double r1 = r12[2 * i], r2 = r12[2 * i + 1];
+    sp = ((r1 * ld3(L.su) + r2 * ld3(L.sv)) + ld3(L.pos)) + ld3(L.dir) * kEps;
+    if (use_mask) em = occluder_mask(S, L, p);
+  } else {
+    sp = ld3(p_in + 3 * i);
+  }
+  Counts cnt = {};
+  lit[i] = illum_test<KINDS>(S, p, sp, cnt, em) ? 1 : 0;
+  p_light[3 * i] = sp.x; p_light[3 * i + 1] = sp.y; p_light[3 * i + 2] = sp.z;
+}
+
 // ---------------------------------------------------------------------------------------
 // host-callable launchers
 // ---------------------------------------------------------------------------------------
@@ -2096,6 +2139,44 @@ void launch_intersect(const SceneView &S, int64_t n, const double *org, const do
                       hipStream_t st) {
   if (n == 0) return;
   intersect_kernel<<<nblk(n, 128), 128, 0, st>>>(S, n, org, dir, hit, t, point, normal, mat);
+}
+
+// The probes' instance selector: 0 = the instance with_kinds picks for the scene (the render's),
+// 1 = KINDS_ALL, 2 = KINDS_TRI_SPHERE, 3 = KINDS_POLY. f gets the instance as with_kinds hands it
+// over; false (and no call) for an unknown selector or an instance that does not hold the scene's
+// kinds.
+template <class F>
+static bool with_instance(const SceneView &S, int instance, F f) {
+  switch (instance) {
+    case 0: with_kinds(S, f); return true;
+    case 1: f(std::integral_constant<uint32_t, KINDS_ALL>{}); return true;
+    case 2:
+      if (!kinds_within(S.kinds, KINDS_TRI_SPHERE)) return false;
+      f(std::integral_constant<uint32_t, KINDS_TRI_SPHERE>{});
+      return true;
+    case 3:
+      if (!kinds_within(S.kinds, KINDS_POLY)) return false;
+      f(std::integral_constant<uint32_t, KINDS_POLY>{});
+      return true;
+    default: return false;
+  }
+}
+bool launch_intersect_probe(const SceneView &S, int instance, int64_t n, const double *org,
+                            const double *dir, const int32_t *hint, int32_t *hit, double *t,
+                            double *point, double *normal, int32_t *mat, int32_t *tri,
+                            hipStream_t st) {
+  return with_instance(S, instance, [&](auto K) {
+    intersect_probe_kernel<K.value><<<nblk(n, 128), 128, 0, st>>>(S, n, org, dir, hint, hit, t, point,
+                                                                 normal, mat, tri);
+  });
+}
+bool launch_illum_probe(const SceneView &S, int instance, int64_t n, const double *p_scene,
+                        const int32_t *light, const double *r12, const double *p_in, int use_mask,
+                        double *p_light, int32_t *lit, hipStream_t st) {
+  return with_instance(S, instance, [&](auto K) {
+    illum_probe_kernel<K.value><<<nblk(n, 128), 128, 0, st>>>(S, n, p_scene, light, r12, p_in,
+                                                             use_mask, p_light, lit);
+  });
 }
 
 }  // namespace gi

@@ -82,12 +82,16 @@ constexpr int GI_MAX_DEPTH = 16;  // scene-graph depth supported on the device
 struct DNode {
   double Tinv[12];     // world(parent)->local rows 0..2 of R4Matrix inverse
   double T[12];        // local->parent
+  // bounding box in the parent's coordinates (R3SceneNode::UpdateBBox, R3SceneNode.cpp:540-560:
+  // the union of the transformed boxes of the elements and of the children); a ray that fails
+  // R3SceneNode::Intersects' test of it (:438-442) skips the node and its subtree
+  double bmin[3], bmax[3];
   int32_t parent;      // -1 for root
   int32_t identity;    // transform is exactly the identity
   int32_t elem_first, elem_count;
   int32_t depth;       // nodes on the path root..this node
   int32_t chain[GI_MAX_DEPTH];  // that path, root first (precomputed: no per-ray walk)
-  int32_t pad;
+  int32_t skip;        // the node after this node's subtree (pre-order)
 };
 
 struct DMaterial {

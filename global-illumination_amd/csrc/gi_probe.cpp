@@ -403,4 +403,158 @@ int gi_intersect_batch(gi_ctx *c, int64_t n, const double *org, const double *di
   return GI_OK;
 }
 
+int gi_intersect_probe(gi_ctx *c, int64_t n, const double *org, const double *dir,
+                       const int32_t *hint, int instance, int32_t *hit, double *t, double *point,
+                       double *normal, int32_t *material, int32_t *tri) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded");
+  if (n < 0 || (n > 0 && (!org || !dir || !hit || !t || !point || !normal || !material || !tri)))
+    return fail(c, GI_ERR_ARG, "intersect probe: missing array");
+  const int64_t ntris = (int64_t)c->scene.tris.size();
+  if (hint)
+    for (int64_t i = 0; i < n; i++)
+      if (hint[i] < -1 || hint[i] >= ntris) return fail(c, GI_ERR_ARG, "intersect probe: hint out of range");
+  if (n == 0) return GI_OK;
+  DeviceScope scope(c->device);
+  DBuf dorg, ddir, dhint, dhit, dt, dp, dn, dm, dtri;
+  HIPCHK(c, upload(dorg, org, (size_t)n * 24, c->stream));
+  HIPCHK(c, upload(ddir, dir, (size_t)n * 24, c->stream));
+  if (hint) HIPCHK(c, upload(dhint, hint, (size_t)n * 4, c->stream));
+  HIPCHK(c, dhit.ensure((size_t)n * 4));
+  HIPCHK(c, dt.ensure((size_t)n * 8));
+  HIPCHK(c, dp.ensure((size_t)n * 24));
+  HIPCHK(c, dn.ensure((size_t)n * 24));
+  HIPCHK(c, dm.ensure((size_t)n * 4));
+  HIPCHK(c, dtri.ensure((size_t)n * 4));
+  if (!launch_intersect_probe(make_view(c), instance, n, dorg.as<double>(), ddir.as<double>(),
+                              hint ? dhint.as<int32_t>() : nullptr, dhit.as<int32_t>(),
+                              dt.as<double>(), dp.as<double>(), dn.as<double>(), dm.as<int32_t>(),
+                              dtri.as<int32_t>(), c->stream))
+    return fail(c, GI_ERR_ARG, "intersect probe: the instance does not hold the scene's shape kinds");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(hit, dhit.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t, dt.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(point, dp.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(normal, dn.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(material, dm.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tri, dtri.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+int gi_illum_probe(gi_ctx *c, int64_t n, const double *p_scene, const int32_t *light,
+                   const double *r12, const double *p_light_in, int use_mask, int instance,
+                   double *p_light_out, int32_t *lit) {
+  if (!c) return GI_ERR_ARG;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded");
+  if (n < 0 || (n > 0 && (!p_scene || !light || !p_light_out || !lit)))
+    return fail(c, GI_ERR_ARG, "illum probe: missing array");
+  const auto &lights = c->scene.lights;
+  for (int64_t i = 0; i < n; i++) {
+    const int li = light[i];
+    if (li < -1 || li >= (int)lights.size()) return fail(c, GI_ERR_ARG, "illum probe: light out of range");
+    if (li < 0) {
+      if (use_mask) return fail(c, GI_ERR_ARG, "illum probe: the mask needs a light");
+      if (!p_light_in) return fail(c, GI_ERR_ARG, "illum probe: light -1 needs p_light_in");
+    } else {
+      if (lights[li].kind != LK_AREA && lights[li].kind != LK_RECT)
+        return fail(c, GI_ERR_ARG, "illum probe: sample coefficients and the mask need an area or rect light");
+      if (!r12) return fail(c, GI_ERR_ARG, "illum probe: a light needs r12");
+    }
+  }
+  if (n == 0) return GI_OK;
+  DeviceScope scope(c->device);
+  DBuf dps, dl, dr, dpi, dpo, dv;
+  HIPCHK(c, upload(dps, p_scene, (size_t)n * 24, c->stream));
+  HIPCHK(c, upload(dl, light, (size_t)n * 4, c->stream));
+  if (r12) HIPCHK(c, upload(dr, r12, (size_t)n * 16, c->stream));
+  if (p_light_in) HIPCHK(c, upload(dpi, p_light_in, (size_t)n * 24, c->stream));
+  HIPCHK(c, dpo.ensure((size_t)n * 24));
+  HIPCHK(c, dv.ensure((size_t)n * 4));
+  if (!launch_illum_probe(make_view(c), instance, n, dps.as<double>(), dl.as<int32_t>(),
+                          r12 ? dr.as<double>() : nullptr, p_light_in ? dpi.as<double>() : nullptr,
+                          use_mask ? 1 : 0, dpo.as<double>(), dv.as<int32_t>(), c->stream))
+    return fail(c, GI_ERR_ARG, "illum probe: the instance does not hold the scene's shape kinds");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(p_light_out, dpo.p, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(lit, dv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GI_OK;
+}
+
+int gi_scene_slab_boxes(const char *scene_path, int64_t capacity, double *boxes, int64_t *count) {
+  if (!scene_path || !count) return GI_ERR_ARG;
+  HostScene H;
+  std::string err;
+  if (!load_scene(scene_path, false, H, err)) return GI_ERR_IO;
+  int64_t n = 0;
+  auto put = [&](int kind, int node, const double *lo, const double *hi) {
+    if (boxes && n < capacity) {
+      double *o = boxes + 20 * n;
+      int ntx = 0;
+      const DNode *tx = nullptr;
+      for (int k = node; k >= 0; k = H.nodes[k].parent)
+        if (!H.nodes[k].identity) { ntx++; tx = &H.nodes[k]; }
+      o[0] = kind;
+      o[1] = ntx <= 1 ? 1.0 : 0.0;
+      for (int i = 0; i < 3; i++) { o[2 + i] = lo[i]; o[5 + i] = hi[i]; }
+      for (int i = 0; i < 12; i++) o[8 + i] = (ntx == 1) ? tx->Tinv[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    }
+    n++;
+  };
+  for (const DElement &el : H.elems) {
+    put(0, el.node, el.pmin, el.pmax);
+    for (int s = el.shape_first; s < el.shape_first + el.shape_count; s++) {
+      const DShape &sh = H.shapes[s];
+      if (sh.kind != SK_MESH || sh.bvh_first < 0) continue;
+      const int end = H.bvh[sh.bvh_first].skip;
+      for (int b = 0; b < end; b++) put(1, el.node, H.bvh[sh.bvh_first + b].lo, H.bvh[sh.bvh_first + b].hi);
+    }
+  }
+  *count = n;
+  if (boxes && capacity < n) return GI_ERR_ARG;
+  return GI_OK;
+}
+
+int gi_scene_triangle_planes(gi_ctx *c, int64_t capacity, double *planes, int64_t *count) {
+  if (!c || !count) return GI_ERR_ARG;
+  if (!c->have_scene) return fail(c, GI_ERR_STATE, "no scene loaded");
+  const HostScene &H = c->scene;
+  *count = (int64_t)H.tris.size();
+  if (!planes) return GI_OK;
+  if (capacity < *count) return fail(c, GI_ERR_ARG, "triangle planes: capacity too small");
+  auto up = [&](int node, double *p) {  // a point of `node`'s frame in world coordinates
+    for (int k = node; k >= 0; k = H.nodes[k].parent) {
+      const DNode &a = H.nodes[k];
+      if (a.identity) continue;
+      const double x = p[0], y = p[1], z = p[2];
+      for (int r = 0; r < 3; r++) p[r] = a.T[4 * r] * x + a.T[4 * r + 1] * y + a.T[4 * r + 2] * z + a.T[4 * r + 3];
+    }
+  };
+  for (const DElement &el : H.elems)
+    for (int s = el.shape_first; s < el.shape_first + el.shape_count; s++) {
+      const DShape &sh = H.shapes[s];
+      const int cnt = sh.kind == SK_TRI ? 1 : (sh.kind == SK_MESH ? sh.tri_count : 0);
+      for (int i = 0; i < cnt; i++) {
+        const DTri &tr = H.tris[sh.tri_first + i];
+        // three points of the plane: p0 and p0 plus two tangents (-edge-plane normals lie in it)
+        double q[3][3];
+        for (int r = 0; r < 3; r++) {
+          q[0][r] = tr.p0[r];
+          q[1][r] = tr.p0[r] + tr.ev[0][r];
+          q[2][r] = tr.p0[r] + tr.ev[1][r];
+        }
+        for (int k = 0; k < 3; k++) up(el.node, q[k]);
+        const double a[3] = {q[1][0] - q[0][0], q[1][1] - q[0][1], q[1][2] - q[0][2]};
+        const double b[3] = {q[2][0] - q[0][0], q[2][1] - q[0][1], q[2][2] - q[0][2]};
+        double nn[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        const double l = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
+        double *o = planes + 4 * (size_t)(sh.tri_first + i);
+        for (int r = 0; r < 3; r++) o[r] = l > 0 ? nn[r] / l : 0.0;
+        o[3] = -(o[0] * q[0][0] + o[1] * q[0][1] + o[2] * q[0][2]);
+      }
+    }
+  return GI_OK;
+}
+
 }  // extern "C"

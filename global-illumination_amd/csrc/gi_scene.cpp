@@ -582,7 +582,7 @@ static Bx flatten(Graph &G, int gi_idx, int parent, HostScene &S) {
   dn.elem_first = (int)S.elems.size();
   dn.elem_count = (int)g.elems.size();
   S.nodes.push_back(dn);
-  Bx local;
+  Bx out;
   for (auto &e : g.elems) {
     DElement de;
     memset(&de, 0, sizeof de);
@@ -622,18 +622,19 @@ static Bx flatten(Graph &G, int gi_idx, int parent, HostScene &S) {
       de.pmax[i] = eb.mx[i] + m;
     }
     S.elems.push_back(de);
-    local.add(eb);
+    xform_box(g.T, eb, out);  // each box transformed on its own, then united (UpdateBBox)
   }
   // elements are contiguous per node only if children are appended after: gather children
   std::vector<int> kids = g.children;
-  Bx kb;
   for (int c : kids) {
     Bx cb = flatten(G, c, id, S);
-    kb.add(cb);
+    xform_box(g.T, cb, out);
   }
-  local.add(kb);
-  Bx out;
-  xform_box(g.T, local, out);
+  for (int i = 0; i < 3; i++) {
+    S.nodes[id].bmin[i] = out.mn[i];
+    S.nodes[id].bmax[i] = out.mx[i];
+  }
+  S.nodes[id].skip = (int)S.nodes.size();
   return out;
 }
 

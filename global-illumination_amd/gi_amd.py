@@ -70,6 +70,8 @@ EXPORTED = [
     "gi_accum_merge_packed", "gi_accum_merge_from",
     "gi_progressive_params_default", "gi_progressive_radius", "gi_accum_add_progressive",
     "gi_estimate_radiance_batch", "gi_knn_batch", "gi_knn_bench", "gi_intersect_batch",
+    "gi_intersect_probe", "gi_illum_probe", "gi_scene_triangle_planes",
+    "gi_scene_slab_boxes",
     "gi_math_probe", "gi_release_scratch",
     "gi_write_image", "gi_write_image_float",
 ]
@@ -337,6 +339,13 @@ def lib():
         L.gi_intersect_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+        L.gi_intersect_probe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.gi_illum_probe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gi_scene_triangle_planes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p,
+                                               P(C.c_int64)]
+        L.gi_scene_slab_boxes.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, P(C.c_int64)]
         L.gi_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
@@ -1070,6 +1079,63 @@ class Renderer:
                                              nr.ctypes.data, m.ctypes.data))
         return hit, t, p, nr, m
 
+    def IntersectProbe(self, org, dirs, hint=None, instance=0):
+        """Intersects through a chosen instance of the scene walk (gi_intersect_probe): 0 the
+        render's for the loaded scene, 1 every shape kind, 2 triangles and spheres, 3 those plus
+        meshes and boxes. hint: per ray, the triangle it leaves from (-1 none). Returns (hit, t,
+        point, normal, material, tri)."""
+        org = np.ascontiguousarray(org, dtype=np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = len(org)
+        assert len(dirs) == n
+        if hint is not None:
+            hint = np.ascontiguousarray(hint, dtype=np.int32).ravel()
+            assert len(hint) == n
+        hit = np.zeros(n, dtype=np.int32)
+        t = np.zeros(n, dtype=np.float64)
+        p = np.zeros((n, 3), dtype=np.float64)
+        nr = np.zeros((n, 3), dtype=np.float64)
+        m = np.zeros(n, dtype=np.int32)
+        tri = np.zeros(n, dtype=np.int32)
+        self._check(lib().gi_intersect_probe(
+            self._ctx, n, org.ctypes.data, dirs.ctypes.data,
+            None if hint is None else hint.ctypes.data, instance, hit.ctypes.data, t.ctypes.data,
+            p.ctypes.data, nr.ctypes.data, m.ctypes.data, tri.ctypes.data))
+        return hit, t, p, nr, m, tri
+
+    def IllumProbe(self, p_scene, light, r12=None, p_light=None, mask=False, instance=0):
+        """RayIlluminationTest as the soft-light loops run it (gi_illum_probe). light: one index
+        or one per ray; an area or rect light takes the sample coefficients r12 [n, 2], -1 takes
+        the points p_light [n, 3]. mask: apply the fan's occluder mask. Returns (lit [n] int32,
+        the points on the light [n, 3])."""
+        ps = np.ascontiguousarray(p_scene, dtype=np.float64).reshape(-1, 3)
+        n = len(ps)
+        li = np.ascontiguousarray(np.broadcast_to(np.asarray(light, dtype=np.int32), (n,)))
+        if r12 is not None:
+            r12 = np.ascontiguousarray(r12, dtype=np.float64).reshape(-1, 2)
+            assert len(r12) == n
+        if p_light is not None:
+            p_light = np.ascontiguousarray(p_light, dtype=np.float64).reshape(-1, 3)
+            assert len(p_light) == n
+        out = np.zeros((n, 3), dtype=np.float64)
+        lit = np.zeros(n, dtype=np.int32)
+        self._check(lib().gi_illum_probe(
+            self._ctx, n, ps.ctypes.data, li.ctypes.data,
+            None if r12 is None else r12.ctypes.data,
+            None if p_light is None else p_light.ctypes.data, int(bool(mask)), instance,
+            out.ctypes.data, lit.ctypes.data))
+        return lit, out
+
+    def triangle_planes(self):
+        """World-space planes [ntris, 4] (unit normal, offset) of the loaded scene's triangles,
+        indexed as IntersectProbe's tri (gi_scene_triangle_planes)."""
+        cnt = C.c_int64(0)
+        self._check(lib().gi_scene_triangle_planes(self._ctx, 0, None, C.byref(cnt)))
+        out = np.zeros((cnt.value, 4), dtype=np.float64)
+        self._check(lib().gi_scene_triangle_planes(self._ctx, cnt.value, out.ctypes.data,
+                                                   C.byref(cnt)))
+        return out
+
 
 MATH_FNS = {"acos": 0, "sin": 1, "cos": 2, "pow": 3, "atan2": 4, "sqrt": 5, "tan": 6, "asin": 7}
 
@@ -1081,6 +1147,20 @@ def math_probe(renderer, fn, x, y=None):
     out = np.zeros_like(x)
     renderer._check(lib().gi_math_probe(renderer._ctx, MATH_FNS[fn], len(x), x.ctypes.data,
                                         y.ctypes.data, out.ctypes.data))
+    return out
+
+
+def slab_boxes(scene_path):
+    """The boxes of a scene file's slab tests as the loader builds them (gi_scene_slab_boxes; no
+    device needed): [n, 20] rows of kind, simple, lo[3], hi[3], inverse transform rows [12]."""
+    cnt = C.c_int64(0)
+    rc = lib().gi_scene_slab_boxes(scene_path.encode(), 0, None, C.byref(cnt))
+    if rc != GI_OK:
+        raise GiError(f"gi_scene_slab_boxes({scene_path}) rc={rc}")
+    out = np.zeros((cnt.value, 20), dtype=np.float64)
+    rc = lib().gi_scene_slab_boxes(scene_path.encode(), cnt.value, out.ctypes.data, C.byref(cnt))
+    if rc != GI_OK:
+        raise GiError(f"gi_scene_slab_boxes({scene_path}) rc={rc}")
     return out
 
 

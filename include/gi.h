@@ -738,6 +738,40 @@ int gi_adaptive_bench(gi_ctx *ctx, int width, int height, int tile_px, int warmu
                       double *select_ms, double *masked_merge_ms, double *merge_ms);
 int gi_intersect_batch(gi_ctx *ctx, int64_t n, const double *org, const double *dir,
                        int32_t *hit, double *t, double *point, double *normal, int32_t *material);
+/* Test seam: gi_intersect_batch through a chosen instance of the scene walk. hint: per ray, the
+ * triangle the ray leaves from (an index as `tri` returns it; the walk tests it first), -1 for
+ * none; NULL = every ray -1. tri: the triangle hit, an index into the loaded scene's triangles in
+ * loading order (triangle shapes and mesh triangles, element by element; mesh triangles in the
+ * order of the mesh's hierarchy), -1 for other shapes and for a miss. instance: 0 = the instance
+ * a render launches for the loaded scene (the smallest that holds its shape kinds), 1 = the one
+ * for every kind, 2 = triangles and spheres only, 3 = those plus meshes and boxes; an instance
+ * that does not hold the scene's kinds is GI_ERR_ARG. GI_ELEM_PRETEST applies as in a render. */
+int gi_intersect_probe(gi_ctx *ctx, int64_t n, const double *org, const double *dir,
+                       const int32_t *hint, int instance, int32_t *hit, double *t, double *point,
+                       double *normal, int32_t *material, int32_t *tri);
+/* Test seam: RayIlluminationTest (illumination_utils.cpp:16-31) as the soft-light loops call it.
+ * Per ray: the shaded point p_scene and a light index. light[i] >= 0 names an area or rect light
+ * (else GI_ERR_ARG): the point on it is ((r1 u + r2 v) + centre) + normal * 1e-6 with (r1, r2) =
+ * r12[2i], r12[2i + 1] (illumination_utils.cpp:150-157, 315-319: r in the unit disk for an area
+ * light, in [-1/2, 1/2]^2 for a rect light). light[i] == -1 takes the point p_light_in[3i..].
+ * use_mask: the fan's occluder mask of (light, p_scene) limits the elements searched, as in a
+ * render with 16 or more samples per fan; it needs light[i] >= 0 for every ray (else GI_ERR_ARG).
+ * instance as in gi_intersect_probe. Outputs: the point on the light used, and lit = 1 when the
+ * point sees it, 0 when not. r12 / p_light_in may be NULL when no ray reads them. */
+int gi_illum_probe(gi_ctx *ctx, int64_t n, const double *p_scene, const int32_t *light,
+                   const double *r12, const double *p_light_in, int use_mask, int instance,
+                   double *p_light_out, int32_t *lit);
+/* Test seam: the world-space plane (unit normal n, offset d: n . x + d = 0) of every triangle of
+ * the loaded scene, four doubles each, indexed as gi_intersect_probe's `tri`. *count = their
+ * number; planes == NULL only reports it. */
+int gi_scene_triangle_planes(gi_ctx *ctx, int64_t capacity, double *planes, int64_t *count);
+/* Test seam, needs no context or device: the boxes of the scene file's two division-free slab
+ * tests as the loader builds them, 20 doubles each: kind (0 = an element's box grown for the
+ * element pre-test, 1 = a box of a mesh's hierarchy), simple (1 when at most one node on the
+ * path from the root to the box's node has a transform), lo[3], hi[3] in the node's frame, and
+ * rows 0..2 of that one transform's inverse (parent -> node; the identity when there is none).
+ * *count = their number; boxes == NULL only reports it. */
+int gi_scene_slab_boxes(const char *scene_path, int64_t capacity, double *boxes, int64_t *count);
 /* Test seam: the device's fp64 math on host inputs, fn = 0 acos(x), 1 sin(x), 2 cos(x),
  * 3 pow(x, y), 4 atan2(x, y), 5 sqrt(x), 6 tan(x), 7 asin(x) (y ignored except by 3 and 4): the
  * functions the photon tracer, samplers and Phong terms call (graphics_utils.cpp:95-216,

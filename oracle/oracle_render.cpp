@@ -1917,6 +1917,32 @@ int oracle_intersect(const char *scene_path, int64_t n, const double *org, const
   return 0;
 }
 
+// RayIlluminationTest for a batch of (point in the scene, point on the light) pairs
+int oracle_illum_test(const char *scene_path, int64_t n, const double *p_scene,
+                      const double *p_light, int32_t *lit) {
+  Ctx c;
+  std::string err;
+  if (!read_scene(scene_path, false, c.scene, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+  Counters cnt;
+  for (int64_t i = 0; i < n; i++)
+    lit[i] = ray_illumination_test(c, V3(p_scene[3 * i], p_scene[3 * i + 1], p_scene[3 * i + 2]),
+                                   V3(p_light[3 * i], p_light[3 * i + 1], p_light[3 * i + 2]), cnt)
+                 ? 1 : 0;
+  return 0;
+}
+
+// per ray, scene_tri_ties (fixture census of rays through shared edges and vertices)
+int oracle_tri_ties(const char *scene_path, int64_t n, const double *org, const double *dir,
+                    int32_t *ties) {
+  Scene s;
+  std::string err;
+  if (!read_scene(scene_path, false, s, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+  for (int64_t i = 0; i < n; i++)
+    ties[i] = scene_tri_ties(s, V3(org[3 * i], org[3 * i + 1], org[3 * i + 2]),
+                             V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+  return 0;
+}
+
 // RGBE codec + direction LUT known-answer helpers
 void oracle_rgbe_encode(const double *rgb, uint8_t *out) { rgb_to_rgbe(Rgb(rgb[0], rgb[1], rgb[2]), out); }
 void oracle_rgbe_decode(const uint8_t *in, double *rgb) {

@@ -387,6 +387,33 @@ bool scene_intersect(const Scene &s, V3 org, V3 dir, Hit &h) {
   return node_intersect(s, 0, org, dir, 0.0, RN_INF, h);
 }
 
+// Test-fixture census (no reference counterpart): the ray taken down the graph as node_intersect
+// takes it, without any box test; per node, the triangles ray_tri accepts, and of those the ones
+// whose t equals the node's smallest accepted t bit for bit. Returns the largest such count.
+static int node_tri_ties(const Scene &s, int ni, V3 org, V3 dir) {
+  const Node &nd = s.nodes[ni];
+  V3 norg = nd.Tinv.point(org);
+  V3 ndir = normalize(nd.Tinv.vec(dir));
+  if (isNegOrZero(length(nd.T.vec(dir)))) return 0;
+  double best = FLT_MAX;
+  int ties = 0;
+  auto take = [&](const Tri &tr) {
+    double t;
+    V3 p;
+    if (!ray_tri(norg, ndir, tr, t, p)) return;
+    if (t < best) { best = t; ties = 1; }
+    else if (t == best) ties++;
+  };
+  for (const Element &el : nd.elements)
+    for (const Shape &sh : el.shapes) {
+      if (sh.type == SH_TRI) take(sh.tri);
+      if (sh.type == SH_MESH) for (const Tri &tr : sh.tris) take(tr);
+    }
+  for (int ci : nd.children) ties = std::max(ties, node_tri_ties(s, ci, norg, ndir));
+  return ties;
+}
+int scene_tri_ties(const Scene &s, V3 org, V3 dir) { return node_tri_ties(s, 0, org, dir); }
+
 // ---------------------------------------------------------------------------------------
 // Loader
 // ---------------------------------------------------------------------------------------

@@ -130,6 +130,8 @@ struct Hit {
 };
 // R3Scene::Intersects (R3Scene.cpp:471-479), min_t = 0, max_t = RN_INFINITY
 bool scene_intersect(const Scene &s, V3 org, V3 dir, Hit &h);
+// how many triangles of one node accept the ray at that node's smallest triangle t (fixtures)
+int scene_tri_ties(const Scene &s, V3 org, V3 dir);
 
 // R3Intersects(ray, box) (R3Isect.cpp:883-942)
 int ray_box(V3 org, V3 dir, const Box &b, double *t, V3 *normal);

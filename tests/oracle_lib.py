@@ -111,6 +111,35 @@ def intersect(scene, org, dirs):
     return hit, t, p, nr, m
 
 
+def illum_test(scene, p_scene, p_light):
+    """RayIlluminationTest (oracle_illum_test) of each (point in the scene, point on the light)
+    pair: 1 lit, 0 not."""
+    ps = np.ascontiguousarray(p_scene, dtype=np.float64).reshape(-1, 3)
+    pl = np.ascontiguousarray(p_light, dtype=np.float64).reshape(-1, 3)
+    assert len(ps) == len(pl)
+    L = lib()
+    L.oracle_illum_test.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lit = np.zeros(len(ps), dtype=np.int32)
+    rc = L.oracle_illum_test(scene.encode(), len(ps), ps.ctypes.data, pl.ctypes.data,
+                             lit.ctypes.data)
+    assert rc == 0
+    return lit
+
+
+def tri_ties(scene, org, dirs):
+    """Per ray, how many triangles of one scene node accept it at that node's smallest triangle
+    t, bit for bit (oracle_tri_ties): 2 or more on a shared edge or vertex."""
+    org = np.ascontiguousarray(org, dtype=np.float64).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    L = lib()
+    L.oracle_tri_ties.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    ties = np.zeros(len(org), dtype=np.int32)
+    rc = L.oracle_tri_ties(scene.encode(), len(org), org.ctypes.data, dirs.ctypes.data,
+                           ties.ctypes.data)
+    assert rc == 0
+    return ties
+
+
 def parse_args(args):
     from gi_amd import GiParams
     n, argv = _argv(args)

@@ -55,6 +55,21 @@ def test_scene_full_gi_matches_oracle(renderer, path):
     compare_exact(g, o)
 
 
+@pytest.mark.parametrize("name", ["softshadow.scn", "jensen.scn"])
+def test_soft_light_fans_match_oracle(renderer, name):
+    """Direct light only, with 16 light and 16 shadow samples per fan: at 16 or more samples
+    soft_light applies its occluder mask (gi_device.h occluder_mask), which the other renders
+    here (-lt 4 -ss 4) never reach."""
+    args = [os.path.join(INP, name), "/tmp/s.png", "-resolution", "32", "24", "-aa", "0",
+            "-no_indirect", "-no_caustic", "-seed", "6", "-lt", "16", "-ss", "16", "-tt", "4",
+            "-st", "4", "-md", "32"]
+    g, gst, _ = run_gpu(renderer, args)
+    o, ost = oracle_lib.render(args, 32, 24)
+    assert gst["screen_rays"] == ost["screen_rays"]
+    assert gst["shadow_rays"] == ost["shadow_rays"] and gst["shadow_rays"] > 16 * 32 * 24
+    compare_exact(g, o)
+
+
 def test_circle_intersections_match_oracle(renderer):
     """R3Intersects(ray, R3Circle) (R3Isect.cpp:837-879; gi_device.h ray_circle): rays aimed at
     points inside, on and just outside each circle of circles.scn, from both sides."""
@@ -85,10 +100,10 @@ def test_circle_intersections_match_oracle(renderer):
     oh, ot, op, on, om = oracle_lib.intersect(path, org, d)
     assert gh.sum() > 0.5 * len(gh)
     np.testing.assert_array_equal(gh, oh)
-    both = gh == 1
-    np.testing.assert_allclose(gt[both], ot[both], rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(gn[both], on[both], atol=1e-12)
-    np.testing.assert_array_equal(gm[both], om[both])
+    np.testing.assert_array_equal(gt, ot)
+    np.testing.assert_array_equal(gp, op)
+    np.testing.assert_array_equal(gn, on)
+    np.testing.assert_array_equal(gm, om)
 
 
 def test_device_math_equals_oracle_math(renderer):
